@@ -10,13 +10,18 @@ offline), decoder noise drawn per step as in eval.py.  PNG encoding is not
 timed.  One process per GPU (torchrun); faces shard across ranks with no
 data-path collective (weak scaling): value = all faces / max-over-ranks time.
 
-Also reported: the dominant kernel's roofline (the fused field kernel, MFMA
-bound) from HIP events recorded on the renderer's stream around that kernel
-during the timed steps, the hash-grid gather kernel's HBM-roofline fraction,
-a CPU baseline (the oracle renderer + PyTorch-CPU decoder) on the host cores
-for a bounded sample, and after the timed region, outside
-`value`: faces/s at B = 1 (eval.py's own batch) and 8, and at B with every
-image copied to pinned host memory ("with host copy").
+A plain run sets up, warms up, times the steps, writes the last timed step's
+images with --dump-outputs DIR, and prints the result line.  That line also
+carries the dominant kernel's roofline (the fused field kernel, MFMA bound) and
+the hash-grid gather kernel's HBM-roofline fraction: both come from HIP events
+recorded on the renderer's stream during the timed steps themselves, so they
+take no run of their own.
+
+With --full, after the timed region and outside `value`: a CPU baseline (the
+oracle renderer + PyTorch-CPU decoder) on the host cores for a bounded sample,
+and faces/s at B = 1 (eval.py's own batch) and 8, at B with
+every image copied to pinned host memory ("with host copy"), and one step on
+the exact-fp32 field kernel.
 """
 from __future__ import annotations
 
@@ -58,7 +63,14 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--batch", type=int, default=32, help="faces per step per GPU")
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure the CPU baseline and the extras "
+                        "(B = 1 / 8, host copy, exact-fp32 field); a plain run does neither")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's images (what Generator.forward "
+                        "returned) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baseline")
     p.add_argument("--field-precision", default="f16x3", choices=["f16x3", "fp32"],
                    help="field-stage GEMM arithmetic (DESIGN.md section 5)")
     p.add_argument("--net", default="ngp", choices=["ngp", "siren", "fc"],
@@ -67,7 +79,7 @@ def parse():
                         "(rendering.type 'sdf', configs[4]'s generator)")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the B=1/8 and host-copy measurements")
+                   help="with --full: skip the B=1/8 and host-copy measurements")
     p.add_argument("--traffic-json", default=str(REPO / "profiles" / "field_traffic.json"))
     p.add_argument("--counters-json", default=str(REPO / "profiles" / "round6_counters.json"),
                    help="committed SQ counter summary (scripts/summarize_counters.py) quoted "
@@ -241,6 +253,30 @@ def extras(step, B, graphed_step, g, steps=10, warm=5):
             f"faces_per_s_b{B}_with_host_copy": rate(B, host=True), "unit": "faces/s (one GPU)"}
 
 
+DUMP_BYTES = 64 * 10 ** 6          # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write each array of `arrays` (name -> tensor) as out_dir/<name>.npy in float32
+    (float64 stays float64).  Beyond DUMP_BYTES in all, every array is cut to its share
+    of the budget: a seeded, sorted sample of its flattened elements (the same indices
+    for the same shapes, so two runs compare element for element)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    total = sum(a.nbytes for a in host.values())
+    rng = np.random.default_rng(seed)
+    for name, a in host.items():
+        if total > DUMP_BYTES:
+            keep = max(1, int(DUMP_BYTES * (a.nbytes / total)) // a.itemsize)
+            a = a.reshape(-1)[np.sort(rng.integers(0, a.size, size=keep))]
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main():
     args = parse()
     world, rank, device = setup_dist(args)
@@ -257,6 +293,8 @@ def main():
     gen = torch.Generator(device=device)
     gen.manual_seed(1000 + rank)
 
+    last = {}                       # what the latest step's Generator.forward returned
+
     def step(nb=B):
         z = torch.randn(nb, opt.model.style_dim, device=device, generator=gen)
         cam, focal, near, far, _ = sdfr.generate_camera_params(
@@ -264,6 +302,7 @@ def main():
             fov_ang=opt.camera.fov, dist_radius=opt.camera.dist_radius)
         with torch.no_grad():
             rgb, thumb = g([z], cam, focal, near, far, truncation=1, truncation_latent=None)
+        last["rgb"], last["thumb"] = rgb, thumb
         return rgb
 
     # per-step stage events on the renderer's stream: [0] entry, [1] before / [2] after
@@ -314,6 +353,9 @@ def main():
     g.renderer.stage_events = None
     g.renderer.field_event = None
     g.decoder.profile_convs(None)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # before anything else runs the generator again (--full's extras do)
+        dump_outputs(args.dump_outputs, last)
 
     conv_ms = sum(a_.elapsed_time(b_) for pairs in dev_evs[:n_full]
                   for a_, b_ in pairs[:n_conv]) / n_full
@@ -435,7 +477,7 @@ def main():
                               "field": field_ms, "decoder_regular_convs": conv_ms},
         "cpu_baseline": None,
     }
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         gg = sdfr.GraphedGenerator(g)
 
         def graphed_step(nb):
@@ -471,7 +513,7 @@ def main():
                 "field_ms": f32_ms, "flop_per_sample": FLOP_PER_SAMPLE,
                 "field_tflops": FLOP_PER_SAMPLE * samples / (f32_ms * 1e-3) / 1e12,
                 "peak_tflops": MFMA_F32_PEAK_TFLOPS}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.cpu_seconds, siren and not fc, fc)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -8,10 +8,10 @@
 # limit starts nothing further).  Tasks:
 #   smoke                     __graft_entry__.smoke()
 #   tests[=<pytest -k expr>]  the -m gpu suite (parity record -> <out>/parity.json)
-#   bench                     bench.py, default flags (the driver's command)
+#   bench                     bench.py --full (timed steps, then extras and the CPU baseline)
 #   bench_quick               bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras
 #   bench_siren | bench_fc    the other renderers (configs[4])
-#   bench_b1                  bench.py --batch 1 --steps 100 (eval.py's one face per call)
+#   bench_b1                  bench.py --full --batch 1 --steps 100 (eval.py's one face per call)
 #   trace | trace_b1          rocprofv3 --kernel-trace --stats of bench_quick / bench_b1
 #   counters                  SQ counter passes: field kernels (ngp, fc, siren), decoder convs
 #   traffic                   FETCH_SIZE / WRITE_SIZE passes over bench (one pass each)
@@ -53,11 +53,11 @@ for task in "$@"; do
                --timeout 300 --timeout-method thread ;;
     tests=*) step pytest_gpu 900 python -u -m pytest tests -m gpu -q -p no:cacheprovider \
                --timeout 300 --timeout-method thread -k "${task#tests=}" ;;
-    bench) step bench 600 python bench.py ;;
+    bench) step bench 600 python bench.py --full ;;
     bench_quick) step bench_quick 400 python bench.py $BQ ;;
-    bench_siren) step bench_siren 300 python bench.py --net siren --steps 10 --warmup 3 --no-extras ;;
-    bench_fc) step bench_fc 300 python bench.py --net fc --steps 10 --warmup 3 --no-extras ;;
-    bench_b1) step bench_b1 300 python bench.py --batch 1 --steps 100 --warmup 10 --no-cpu-baseline ;;
+    bench_siren) step bench_siren 300 python bench.py --full --net siren --steps 10 --warmup 3 --no-extras ;;
+    bench_fc) step bench_fc 300 python bench.py --full --net fc --steps 10 --warmup 3 --no-extras ;;
+    bench_b1) step bench_b1 300 python bench.py --full --batch 1 --steps 100 --warmup 10 --no-cpu-baseline ;;
     trace) step trace 400 rocprofv3 --kernel-trace --stats --output-format csv \
                -d "$R/$O/prof_trace" -o trace -- python3 "$R/bench.py" $BQ ;;
     trace_b1) step trace_b1 300 rocprofv3 --kernel-trace --stats --output-format csv \

@@ -125,16 +125,23 @@ def test_rccl_world1_stage2_collectives(tmp_path):
     assert res["ddp_vs_plain_diff"] == [], res["ddp_vs_plain_diff"][:10]
 
 
-def test_bench_rccl_world1():
-    """bench.py under torchrun, one rank, process group over RCCL (SDFR_BENCH_DIST=1)."""
+def test_bench_rccl_world1(tmp_path):
+    """bench.py under torchrun, one rank, process group over RCCL (SDFR_BENCH_DIST=1);
+    a plain run: no extras, no CPU baseline, the last step's images in --dump-outputs."""
+    import numpy as np
     env = dict(os.environ, SDFR_BENCH_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", str(REPO / "bench.py"),
            "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
-           "--no-cpu-baseline", "--no-extras"]
+           "--dump-outputs", str(tmp_path / "dump")]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 1 and rec["steps"] == 3 and rec["value"] > 0
+    assert rec["ms_per_step"] > 0 and rec["cpu_baseline"] is None and "extras" not in rec
+    rgb, thumb = np.load(tmp_path / "dump" / "rgb.npy"), np.load(tmp_path / "dump" / "thumb.npy")
+    assert rgb.dtype == np.float32 and rgb.shape == (4, 3, 256, 256) and np.isfinite(rgb).all()
+    assert thumb.dtype == np.float32 and thumb.shape == (4, 3, 64, 64)
+    assert np.isfinite(thumb).all() and float(np.abs(rgb).max()) > 0
