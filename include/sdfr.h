@@ -42,7 +42,7 @@ extern "C" {
 #define SDFR_ELAUNCH (-2)      /* HIP launch or runtime error                 */
 #define SDFR_EUNSUPPORTED (-3) /* valid for the reference, not implemented    */
 
-#define SDFR_ABI_VERSION 13
+#define SDFR_ABI_VERSION 14
 
 int sdfr_abi_version(void);
 /* Thread-local message for the last non-zero status of this thread. */
@@ -277,6 +277,40 @@ int sdfr_render_siren_forward(const sdfr_siren_weights *w,
  * (writes the encoded samples into the workspace).  Same arguments. */
 int sdfr_render_ngp_encode_only(const sdfr_ngp_weights *w,
                                 const sdfr_ngp_render_args *a, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Fused NGP field query at caller-supplied points (ABI 14; no reference native op:
+ * replaces NGPSIRENGenerator.forward, sdf_model.py:1566-1592, evaluated op by op on
+ * cat([points, dirs]) -- e.g. on a cube of points for marching cubes, or at mesh
+ * vertices for their colour).  The hash-grid gather and the split-fp16 field kernel of
+ * sdfr_render_ngp_forward with the caller's points in place of the ray sampler and a
+ * per-sample store in place of compositing: the same packed weights, FiLM vectors and
+ * per-sample arithmetic (f16x3 only), so a point the render samples gets the render's
+ * SDF bit for bit.  A point whose grid coordinate leaves [0,1] in any axis gets zero
+ * grid features and still runs through the MLP (GridEncoder, gridencoder.cu:104-111).
+ * Points are grouped: the N points of a group share one view direction.  The kernel
+ * takes two points of a group per pass, so N = 1 (a direction per point) idles half
+ * of its lanes.  The colour head runs whether or not rgb is wanted.
+ * SDFR_EINVAL before any launch for null pointers, zero sizes, a workspace below
+ * sdfr_query_ngp_workspace_bytes(B, R, N) (about 144 bytes per point of the padded
+ * count B ceil(R/16) 16 N) or 2^25 or more padded points in one call.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfr_ngp_query_args {
+    uint32_t B, R, N;        /* faces; direction groups per face; points per group      */
+    const float *points;     /* [B,R,N,3] NETWORK coordinates: what NGPSIRENGenerator    */
+                             /* .forward receives (normalized_pts, sdf_model.py:349);    */
+                             /* the grid coordinate u = (p + bound) / (2 bound) is formed */
+                             /* inside with the rounded ops of grid.py:149                */
+    const float *dirs;       /* [B,R,3] view direction of each group AS THE NETWORK SEES  */
+                             /* IT (already unit length; not normalised again)            */
+    const float *styles;     /* [B,256] renderer latent                                   */
+    float *sdf;              /* [B,R,N]   sigma_linear output           (required)        */
+    float *rgb;              /* [B,R,N,3] sigmoid(rgb_linear) in [0,1], or NULL           */
+    void *workspace; size_t workspace_bytes;
+    const void *prepacked;   /* as sdfr_ngp_render_args.prepacked, or NULL                */
+} sdfr_ngp_query_args;
+size_t sdfr_query_ngp_workspace_bytes(uint32_t B, uint32_t R, uint32_t N);
+int sdfr_query_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_query_args *a, void *stream);
 
 #ifdef SDFR_ABLATION
 /* Profiling hooks, exported only by `make ABLATION=1` builds (lib_abl/libsdfr.so,

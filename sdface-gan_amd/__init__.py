@@ -11,6 +11,9 @@ Drop-in surface (reference: im2scene/sdf/models/):
   generate_camera_params                                (sdf_utils.py:97-159)
   align_volume, extract_mesh_with_marching_cubes (+ marching_cubes, Mesh:
   HIP, csrc/mesh.hip), xyz2mesh                       (sdf_utils.py:164-223)
+Beyond the reference: VolumeFeatureRenderer.query / Generator.query_field (the field at
+arbitrary points, fused: sdfr_query_ngp_forward), cube_points, sdf_cube, world_to_network,
+color_mesh (meshes from the field itself, vertex colours).
   SDFOptions, vol_render_opt                            (sdf_utils.py:447, training_utils.py:144)
 Beyond the reference: GraphedGenerator (HIP-graph replay of the inference forward).
 """
@@ -22,8 +25,9 @@ from .generator import (Blur, Decoder, EqualLinear, FusedLeakyReLU, Generator,  
                         MappingLinear, ModulatedConv2d, NoiseInjection, PixelNorm, StyledConv,
                         ToRGB, Upsample, fused_leaky_relu, make_kernel, upfirdn2d)
 from .graphs import GraphedGenerator  # noqa: F401
-from .mesh import (Mesh, align_volume, extract_mesh_with_marching_cubes,  # noqa: F401
-                   marching_cubes, xyz2mesh)
+from .mesh import (Mesh, align_volume, color_mesh, cube_points,  # noqa: F401
+                   extract_mesh_with_marching_cubes, marching_cubes, sdf_cube,
+                   world_to_network, xyz2mesh)
 from .options import AttrDict, SDFOptions, vol_render_opt  # noqa: F401
 from . import training  # noqa: F401  (stage-2 DDP trainer, Discriminator, losses)
 from .renderer import (FCGenerator, FiLMSiren, LinearLayer, NGPSIRENGenerator,  # noqa: F401

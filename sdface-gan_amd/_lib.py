@@ -23,7 +23,7 @@ SDFR_OK = 0
 SDFR_EINVAL = -1
 SDFR_ELAUNCH = -2
 SDFR_EUNSUPPORTED = -3
-ABI_VERSION = 13
+ABI_VERSION = 14
 FIELD_F16X3 = 0
 FIELD_FP32 = 1
 
@@ -36,7 +36,8 @@ EXPORTS = (
     "sdfr_grid_encode_backward_ws_bytes", "sdfr_grid_encode_backward_ws",
     "sdfr_sh_encode_forward", "sdfr_sh_encode_backward",
     "sdfr_render_ngp_workspace_bytes", "sdfr_render_ngp_forward",
-    "sdfr_render_ngp_encode_only", "sdfr_debug_sin_probe",
+    "sdfr_render_ngp_encode_only", "sdfr_query_ngp_workspace_bytes", "sdfr_query_ngp_forward",
+    "sdfr_debug_sin_probe",
     "sdfr_debug_sin_rev_probe", "sdfr_camera_extrinsics",
     "sdfr_render_siren_workspace_bytes", "sdfr_render_siren_forward",
     "sdfr_render_pack_bytes", "sdfr_render_ngp_pack", "sdfr_render_siren_pack",
@@ -110,6 +111,15 @@ class NgpRenderArgs(ctypes.Structure):
         ("max_field_segments", _u32),
         ("styles_event", _vp), ("field_event", _vp),
         ("features_split", _vp), ("features_mod", _vp),
+    ]
+
+
+class NgpQueryArgs(ctypes.Structure):
+    """sdfr_ngp_query_args (include/sdfr.h, ABI 14)."""
+    _fields_ = [
+        ("B", _u32), ("R", _u32), ("N", _u32),
+        ("points", _vp), ("dirs", _vp), ("styles", _vp), ("sdf", _vp), ("rgb", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("prepacked", _vp),
     ]
 
 
@@ -192,6 +202,10 @@ def lib():
                                           ctypes.POINTER(NgpRenderArgs), _vp]
     L.sdfr_render_ngp_encode_only.argtypes = [ctypes.POINTER(NgpWeights),
                                               ctypes.POINTER(NgpRenderArgs), _vp]
+    L.sdfr_query_ngp_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_query_ngp_workspace_bytes.argtypes = [_u32, _u32, _u32]
+    L.sdfr_query_ngp_forward.argtypes = [ctypes.POINTER(NgpWeights),
+                                         ctypes.POINTER(NgpQueryArgs), _vp]
     for name in ABLATION_EXPORTS:           # profiling builds only (make ABLATION=1)
         if hasattr(L, name):
             getattr(L, name).argtypes = [_int]

@@ -60,6 +60,7 @@ struct NgpNet {
     static constexpr int kL0 = 2;              // layer-0 k-steps of 16 K
     static constexpr int kViewSteps = 17;      // views-layer k-steps (256 hidden + 16 SH)
     static constexpr bool kFieldR = true;      // field_r_kernel (else field_p_kernel)
+    static constexpr bool kQuery = false;      // field query at caller points (NgpQueryNet)
     // input_linear (LinearLayer, affine: sdf_model.py:37-39) feeds pts_linears.0's
     // linear with no nonlinearity between them (:1574-1577), so the two are ONE affine
     // map W1 (W0 x + b0) + b1 = (W1 W0) x + (W1 b0 + b1), composed once per weight
@@ -83,6 +84,7 @@ struct SirenNet {
     static constexpr int kL0 = 1;
     static constexpr int kViewSteps = 17;
     static constexpr bool kFieldR = false;
+    static constexpr bool kQuery = false;
     static constexpr bool kCompose = false;
     static constexpr bool kSlice2 = false;
     static constexpr int kLayers = 9;          // pts_linears.0-7, views
@@ -108,6 +110,7 @@ struct FcNet {
     static constexpr int kL0 = 4;              // 60 encodings (+ 4 zero pad)
     static constexpr int kViewSteps = 18;      // 256 hidden + 24 view encodings (+ 8 pad)
     static constexpr bool kFieldR = true;
+    static constexpr bool kQuery = false;
     static constexpr bool kCompose = false;
     static constexpr int kLayers = 9;          // x_in, pts_linears.0-6, views
     static constexpr int kFilmN = 9;           // (1/su, bias) per layer; layer 0 per face
@@ -118,6 +121,17 @@ struct FcNet {
         return l == 0 ? kPosIn : (l == 8 ? kW + kPosViews : kW);
     }
     __host__ __device__ static constexpr int film_layer(int f) { return f; }
+};
+// NgpNet in query mode (sdfr_query_ngp_forward, csrc/field_query.hip): field_r_kernel
+// evaluates the field at the caller's points -- H = 1, W = R direction groups, N points
+// per group; the group's unit direction is read from memory (XFieldArgs::g.cam holds
+// dirs [B,R,3]) instead of built from a camera, compositing is compiled out, and every
+// sample stores its SDF ([B,R,N]) and sigmoid(rgb) ([B,R,N,3]).  Same packed weights,
+// FiLM vectors and per-sample arithmetic as the render.  Instantiated in its own
+// translation unit only: co-compiled instantiations of one template perturb each
+// other's register allocation, and the render kernels' code must not move.
+struct NgpQueryNet : NgpNet {
+    static constexpr bool kQuery = true;
 };
 constexpr int kMaxLayers = 9;
 
@@ -201,6 +215,9 @@ __device__ __forceinline__ void xpin(f2v &x) { asm volatile("" : "+v"(x)); }
 #endif
 constexpr bool kRTailPk = SDFR_RTAILPK != 0;
 
+// SDFR_FIELD_QUERY_TU: csrc/field_query.hip includes this file for the field_r_kernel
+// template alone; the non-template kernels and the host code stay in this unit.
+#ifndef SDFR_FIELD_QUERY_TU
 // ----------------------------------------------------------------------------
 // prep 1: per-row power-of-two scales and scaled biases (one wave per row)
 // ----------------------------------------------------------------------------
@@ -249,6 +266,8 @@ __global__ void __launch_bounds__(64) compose_kernel(const float *w0, const floa
     if (j < kFeatIn) wc[(size_t)i * kFeatIn + j] = (float)acc;
     else bc[i] = (float)acc;
 }
+
+#endif  // !SDFR_FIELD_QUERY_TU
 
 // ----------------------------------------------------------------------------
 // prep 2: FiLM vectors (gamma / su) + split-fp16 weight fragments
@@ -384,7 +403,7 @@ __global__ void __launch_bounds__(256) xprep_kernel(const XPrepArgs a) {
 // field kernel
 // ----------------------------------------------------------------------------
 struct XFieldArgs {
-    GeomArgs g;
+    GeomArgs g;                    // (query mode: H = 1, W = R, cam = dirs [B,R,3])
     const float *enc;              // ngp: [L=16][S_total][2]; siren: unused
     const float2 *zd;              // ngp: [S_total] (z, segment length) from the encode kernel
     const f4 *packed;              // [slices][1024]
@@ -1384,6 +1403,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
     constexpr int KL0 = RNet<Net>::kL0;
     constexpr int NS = RNet<Net>::kSteps;
     constexpr int NL = Net::kLayers;
+    constexpr bool Q = Net::kQuery;                         // point query: no ray, no compositing
     __shared__ f4 ring_lds[4 * kRSliceF4];                  // 64 KB weight ring
     __shared__ f4 facc_lds[kRWaves][16][64];                // 64 KB: [wave][f4 of 64 features][lane]
     __shared__ float film_lds[NF * 2 * kW];                 // the workgroup's face
@@ -1417,8 +1437,10 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
     r_dma<2>(R, 2);
     r_dma<3>(R, 3);
     f4 *facc = &facc_lds[wave][0][lane];
+    if constexpr (!Q) {
 #pragma unroll
-    for (int t = 0; t < 16; ++t) facc[t * 64] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int t = 0; t < 16; ++t) facc[t * 64] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -1442,18 +1464,29 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
     const uint32_t ray_index = (b * G.H + py) * G.W + px;
 
     Ray ray;
-    make_ray(G.cam + (size_t)b * 12, G.focal[b], G.pix_x[px], G.pix_y[py], G.half_res, ray);
-    const float nr = G.near_[b], fr = G.far_[b];
+    if constexpr (!Q)
+        make_ray(G.cam + (size_t)b * 12, G.focal[b], G.pix_x[px], G.pix_y[py], G.half_res, ray);
+    const float nr = Q ? 0.0f : G.near_[b], fr = Q ? 0.0f : G.far_[b];
     const float span = __fsub_rn(fr, nr);
-    const float dnorm = norm3_torch(ray.d[0], ray.d[1], ray.d[2]);
+    const float dnorm = Q ? 0.0f : norm3_torch(ray.d[0], ray.d[1], ray.d[2]);
     constexpr int NVX = Net::kViewSteps - 16;
     f4 vx[NVX][2];                                          // the views layer's k-steps 16 (, 17)
     {
-        const float v0 = G.static_viewdirs ? ray.dir[0] : ray.d[0];
-        const float v1 = G.static_viewdirs ? ray.dir[1] : ray.d[1];
-        const float v2 = G.static_viewdirs ? ray.dir[2] : ray.d[2];
-        const float vn = norm3_torch(v0, v1, v2);
-        const float ux = __fdiv_rn(v0, vn), uy = __fdiv_rn(v1, vn), uz = __fdiv_rn(v2, vn);
+        float ux, uy, uz;
+        if constexpr (Q) {
+            // the group's direction as the network sees it (unit length already):
+            // dirs [B,R,3] in G.cam, ray_index = b R + group (H = 1, W = R)
+            const float *dv = G.cam + (size_t)ray_index * 3;
+            ux = dv[0];
+            uy = dv[1];
+            uz = dv[2];
+        } else {
+            const float v0 = G.static_viewdirs ? ray.dir[0] : ray.d[0];
+            const float v1 = G.static_viewdirs ? ray.dir[1] : ray.d[1];
+            const float v2 = G.static_viewdirs ? ray.dir[2] : ray.d[2];
+            const float vn = norm3_torch(v0, v1, v2);
+            ux = __fdiv_rn(v0, vn), uy = __fdiv_rn(v1, vn), uz = __fdiv_rn(v2, vn);
+        }
         float v[8];
         if constexpr (Net::kPosEnc) {
             // transform_points(views, True) (sdf_model.py:1628-1640): p / 2, 4 frequencies
@@ -1666,7 +1699,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
             constexpr int KS = KV + j;
             bf[0] = bn[0];
             bf[1] = bn[1];
-            if constexpr (j == 14 && Net::kGrid) {
+            if constexpr (j == 14 && Net::kGrid && !Q) {
                 const float2 v = a.zd[tile_sid + (size_t)sc_ * kTileRays];
                 z = v.x;
                 dist = v.y;
@@ -1686,7 +1719,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
                 } else if constexpr (j == 16 && gi == 0 && NVX > 1) {
                     bn[0] = vx[NVX - 1][0];                 // fc: k-step 17's B
                     bn[1] = vx[NVX - 1][1];
-                } else if constexpr (j == 15 && gi == 1) {
+                } else if constexpr (j == 15 && gi == 1 && !Q) {
                     if constexpr (!Net::kGrid) {
                         z = sample_z(G.sc, nr, fr, ray_index, sc_);
                         dist = (sc_ + 1 < G.N)
@@ -1704,7 +1737,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
                         alpha = 1.0f - expf(-sp * dist);
                     }
                     al = s_ok ? alpha : 0.0f;
-                } else if constexpr (j == 16 && gi == 1) {
+                } else if constexpr (j == 16 && gi == 1 && !Q) {
                     // the pass's two compositing weights, identically in both lanes of a ray
                     const float ao = __shfl_xor(al, 16);
                     const float aj[2] = {odd ? ao : al, odd ? al : ao};
@@ -1749,7 +1782,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
                 T.w1[u] = *reinterpret_cast<const f4 *>(rgb_w + kW + r0);
                 T.w2[u] = *reinterpret_cast<const f4 *>(rgb_w + 2 * kW + r0);
             }
-            T.fa = facc[(4 * t + bq) * 64];
+            if constexpr (!Q) T.fa = facc[(4 * t + bq) * 64];
         };
         TailIn tin[2];
         tail_load(0, tin[0]);
@@ -1781,16 +1814,18 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
                         fp[u][2 * rp] = fv.x;
                         fp[u][2 * rp + 1] = fv.y;
                     }
-                f4 acc4 = T.fa;
-                const f2v wo = {w_own, w_own};
+                if constexpr (!Q) {
+                    f4 acc4 = T.fa;
+                    const f2v wo = {w_own, w_own};
 #pragma unroll
-                for (int rp = 0; rp < 2; ++rp) {
-                    const f2v pa = wo * f2v{fp[0][2 * rp], fp[0][2 * rp + 1]};
-                    const f2v pb = wo * f2v{fp[1][2 * rp], fp[1][2 * rp + 1]};
-                    acc4[2 * rp] = __fadd_rn(acc4[2 * rp], row_pair_sum(pa.x, pb.x));
-                    acc4[2 * rp + 1] = __fadd_rn(acc4[2 * rp + 1], row_pair_sum(pa.y, pb.y));
+                    for (int rp = 0; rp < 2; ++rp) {
+                        const f2v pa = wo * f2v{fp[0][2 * rp], fp[0][2 * rp + 1]};
+                        const f2v pb = wo * f2v{fp[1][2 * rp], fp[1][2 * rp + 1]};
+                        acc4[2 * rp] = __fadd_rn(acc4[2 * rp], row_pair_sum(pa.x, pb.x));
+                        acc4[2 * rp + 1] = __fadd_rn(acc4[2 * rp + 1], row_pair_sum(pa.y, pb.y));
+                    }
+                    facc[(4 * t + bq) * 64] = acc4;
                 }
-                facc[(4 * t + bq) * 64] = acc4;
 #pragma unroll
                 for (int o = 0; o < 3; ++o)
 #pragma unroll
@@ -1818,14 +1853,16 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
                     fp[u][r] = f;
                 }
             // (accumulated whether or not the call wants features: no branch here)
-            f4 acc4 = T.fa;
+            if constexpr (!Q) {
+                f4 acc4 = T.fa;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float pa = __fmul_rn(w_own, fp[0][r]);
-                const float pb = __fmul_rn(w_own, fp[1][r]);
-                acc4[r] = __fadd_rn(acc4[r], row_pair_sum(pa, pb));
+                for (int r = 0; r < 4; ++r) {
+                    const float pa = __fmul_rn(w_own, fp[0][r]);
+                    const float pb = __fmul_rn(w_own, fp[1][r]);
+                    acc4[r] = __fadd_rn(acc4[r], row_pair_sum(pa, pb));
+                }
+                facc[(4 * t + bq) * 64] = acc4;
             }
-            facc[(4 * t + bq) * 64] = acc4;
             // the dot-product partials are materialised here (IR sinking otherwise defers
             // all 384 fmas past the loop and keeps every colour feature live: spills)
 #pragma unroll
@@ -1848,6 +1885,16 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
             P0 = __fadd_rn(P0, __shfl_xor(P0, 32));
             P1 = __fadd_rn(P1, __shfl_xor(P1, 32));
             P2 = __fadd_rn(P2, __shfl_xor(P2, 32));
+            if constexpr (Q) {
+                // the sample's own colour [B,R,N,3] (the render composites these values)
+                if (a.rgb && ray_ok && h == 0 && s_ok) {
+                    float *o = a.rgb + ((size_t)ray_index * G.N + s_own) * 3;
+                    o[0] = sigmoidf_(__fadd_rn(P0, rgb_b0));
+                    o[1] = sigmoidf_(__fadd_rn(P1, rgb_b1));
+                    o[2] = sigmoidf_(__fadd_rn(P2, rgb_b2));
+                }
+                continue;
+            }
             racc0 = __fmaf_rn(w_own, sigmoidf_(__fadd_rn(P0, rgb_b0)), racc0);
             racc1 = __fmaf_rn(w_own, sigmoidf_(__fadd_rn(P1, rgb_b1)), racc1);
             racc2 = __fmaf_rn(w_own, sigmoidf_(__fadd_rn(P2, rgb_b2)), racc2);
@@ -1863,6 +1910,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
     }
     // the ring runs ahead across passes: no LDS-DMA may land after the workgroup ends
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (Q) return;                                // per-sample stores only
     // the two lanes of a ray (samples 2p, 2p + 1) add their partials
     racc0 = __fadd_rn(racc0, __shfl_xor(racc0, 16));
     racc1 = __fadd_rn(racc1, __shfl_xor(racc1, 16));
@@ -1937,6 +1985,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
     }
 }
 
+#ifndef SDFR_FIELD_QUERY_TU
 // Chains the nseg segment partials of every ray (see kPartQ): one thread per
 // (ray, quantity), quantities on grid.y.
 __global__ void __launch_bounds__(256) field_merge_kernel(const XFieldArgs a) {
@@ -2401,3 +2450,6 @@ int sdfr_render_siren_forward(const sdfr_siren_weights *w, const sdfr_ngp_render
 }
 
 }  // extern "C"
+#else
+}  // namespace sdfr
+#endif  // !SDFR_FIELD_QUERY_TU

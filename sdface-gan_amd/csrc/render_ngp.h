@@ -136,6 +136,14 @@ int launch_xprep_ngp(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, c
 int launch_xfield_ngp(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a,
                       const GeomArgs &g, const float *enc, char *xws, const float *film,
                       hipStream_t st, float *part, const float2 *zd);
+// Field query at caller points (field_query.hip): the points' grid coordinates in tile
+// order (g: H = 1, W = R groups, N points per group), and field_r_kernel in query mode
+// (g.cam = dirs [B,R,3]; xws = the packed weights' region; sdf [B,R,N], rgb [B,R,N,3] or
+// null).
+int launch_query_geom(const float *points, f4 *gu, const GeomArgs &g, hipStream_t st);
+int launch_qfield_ngp(const sdfr_ngp_weights *w, const GeomArgs &g, const float *enc,
+                      const char *xws, const float *film, float *sdf, float *rgb,
+                      hipStream_t st);
 // sample-segment split of the f16x3 field kernel for small batches
 constexpr uint32_t kFieldSplitMax = 4;   // sample segments per ray at most
 uint32_t field_nseg(uint32_t B, uint32_t tiles_per_face, uint32_t N, int force_background,

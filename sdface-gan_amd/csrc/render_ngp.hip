@@ -1160,4 +1160,84 @@ int sdfr_render_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_render_arg
     return SDFR_OK;
 }
 
+// ----------------------------------------------------------------------------
+// field query at caller points (ABI 14): the render's gather and f16x3 field stages
+// with the points given instead of sampled along rays, and the per-sample SDF and
+// colour stored instead of composited (kernels: field_query.hip)
+// ----------------------------------------------------------------------------
+// enc [16][S][2] | film [B][4][2][256] | split-fp16 region | gu [S]; S = 0: too many
+// samples for one call
+static size_t query_ws_layout(uint32_t B, uint32_t R, uint32_t N, uint64_t *S_out,
+                              size_t *o_film = nullptr, size_t *o_x = nullptr,
+                              size_t *o_gu = nullptr) {
+    const uint64_t S = (uint64_t)B * (((uint64_t)R + kTileRays - 1) / kTileRays) * N * kTileRays;
+    if (S_out) *S_out = S;
+    size_t off = align256((size_t)S * 16 * 2 * sizeof(float));
+    if (o_film) *o_film = off;
+    off += align256((size_t)B * kFilm * 2 * kW * sizeof(float));
+    if (o_x) *o_x = off;
+    off += align256(f16x3_ws_bytes(0));
+    if (o_gu) *o_gu = off;
+    off += align256((size_t)S * 4 * sizeof(float));
+    return off;
+}
+
+size_t sdfr_query_ngp_workspace_bytes(uint32_t B, uint32_t R, uint32_t N) {
+    return query_ws_layout(B, R, N, nullptr);
+}
+
+int sdfr_query_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_query_args *a,
+                           void *stream) {
+    if (!w || !a) return fail(SDFR_EINVAL, "query_ngp: null args");
+    if (w->num_levels != 16)
+        return fail(SDFR_EUNSUPPORTED, "query_ngp: fused path needs 16 levels x 2 features");
+    if (a->B == 0 || a->R == 0 || a->N == 0)
+        return fail(SDFR_EINVAL, "query_ngp: empty batch / group / point count");
+    if (!a->points || !a->dirs || !a->styles || !a->sdf || !a->workspace)
+        return fail(SDFR_EINVAL, "query_ngp: required pointer is null");
+    const void *need[] = {w->embeddings, w->offsets, w->input_w, w->input_b, w->views_w,
+                          w->views_b, w->views_gw, w->views_gb, w->views_bw, w->views_bb,
+                          w->sigma_w, w->sigma_b, w->rgb_w, w->rgb_b};
+    for (const void *p : need)
+        if (!p) return fail(SDFR_EINVAL, "query_ngp: weight pointer is null");
+    for (int l = 0; l < 3; ++l)
+        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
+            !w->pts_bb[l])
+            return fail(SDFR_EINVAL, "query_ngp: FiLM weight pointer is null");
+    // the limit of the render (validate: 16 S < 2^32) and the field kernel's 32-bit byte
+    // offsets into enc (128 S < 2^32); group and tile counts fit 32 bits below it
+    uint64_t S;
+    size_t o_film, o_x, o_gu;
+    const size_t need_ws = query_ws_layout(a->B, a->R, a->N, &S, &o_film, &o_x, &o_gu);
+    if (S * 128 >= (1ull << 32) || (uint64_t)a->B * a->R >= (1ull << 32))
+        return fail(SDFR_EINVAL, "query_ngp: too many samples per call (split the points)");
+    if (a->workspace_bytes < need_ws) return fail(SDFR_EINVAL, "query_ngp: workspace too small");
+
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(a->workspace);
+    float *enc = reinterpret_cast<float *>(ws);
+    float *film = reinterpret_cast<float *>(ws + o_film);
+    f4 *gu = reinterpret_cast<f4 *>(ws + o_gu);
+    GeomArgs g{};
+    g.B = a->B;
+    g.H = 1;
+    g.W = a->R;
+    g.N = a->N;
+    g.tiles_per_face = (a->R + kTileRays - 1) / kTileRays;
+    g.total_tiles = a->B * g.tiles_per_face;
+    g.S_total = (uint32_t)S;
+    g.cam = a->dirs;
+    g.bound = w->bound;
+    sdfr_ngp_render_args ra{};            // what the FiLM prep reads of a render call
+    ra.B = a->B;
+    ra.styles = a->styles;
+    ra.prepacked = a->prepacked;
+    int rc;
+    if ((rc = launch_query_geom(a->points, gu, g, st))) return rc;
+    if ((rc = launch_encode(w, &ra, g, enc, gu, st))) return rc;
+    if ((rc = launch_xprep_ngp(w, &ra, ws + o_x, film, st))) return rc;
+    const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
+    return launch_qfield_ngp(w, g, enc, xws, film, a->sdf, a->rgb, st);
+}
+
 }  // extern "C"

@@ -852,6 +852,17 @@ class Generator(nn.Module):
         return self.renderer.mlp_init_pass(cam_poses, focals, near, far, styles=latent[0],
                                            t_rand=t_rand)
 
+    def query_field(self, points, styles, viewdirs=None, truncation=1, truncation_latent=None,
+                    input_is_latent=False, return_rgb=True):
+        """The renderer's field at ``points`` [B,M,3] (network coordinates) for the faces
+        of ``styles``: the mapping network and truncation of ``forward``
+        (``styles_and_noise_forward``), then ``VolumeFeatureRenderer.query`` ->
+        ``(sdf [B,M], rgb [B,M,3] | None)``."""
+        latent = self.styles_and_noise_forward(styles, None, truncation, truncation_latent,
+                                               input_is_latent)
+        lat0 = latent[0][:, 0] if input_is_latent else latent[0]
+        return self.renderer.query(points, lat0, viewdirs=viewdirs, return_rgb=return_rgb)
+
     def forward(self, styles, cam_poses, focals, near=0.88, far=1.12, return_latents=False,
                 inject_index=None, truncation=1, truncation_latent=None, input_is_latent=False,
                 noise=None, randomize_noise=True, return_sdf=False, return_xyz=False,

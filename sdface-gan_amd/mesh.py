@@ -10,6 +10,11 @@ HIP marching cubes (csrc/mesh.hip, ``sdfr_mc_count`` / ``sdfr_mc_emit``) where
 the reference calls scikit-image on the host, applies the reference's vertex
 scaling and axis flips, and returns a ``Mesh`` whose ``export(f, file_type='obj')``
 writes the .obj that sdf_mesh.py:176-182 writes through trimesh.
+
+Beyond the reference, the field can be queried directly (``VolumeFeatureRenderer.query``,
+``sdfr_query_ngp_forward``): ``sdf_cube`` evaluates the SDF on the cube marching cubes
+reads -- no frustum render, no ``align_volume`` resampling -- and ``color_mesh`` asks the
+field for the colour at every vertex (``Mesh.vertex_colors``, written as ``v x y z r g b``).
 """
 from __future__ import annotations
 
@@ -56,16 +61,26 @@ class Mesh:
     ``trimesh.Trimesh`` the reference returns; trimesh's merge / cleanup
     processing is not applied (vertices are already unique per grid edge)."""
 
-    def __init__(self, vertices, faces):
+    def __init__(self, vertices, faces, vertex_colors=None):
         self.vertices = np.asarray(vertices, np.float32)
         self.faces = np.asarray(faces, np.int64)
+        # None, or [V, 3] RGB in [0, 1] (color_mesh)
+        self.vertex_colors = (None if vertex_colors is None
+                              else np.asarray(vertex_colors, np.float32))
 
     def export(self, file_obj=None, file_type="obj"):
-        """Wavefront .obj text (``v x y z`` lines, then 1-based ``f a b c``);
-        written to ``file_obj`` (an open text file or a path) when given."""
+        """Wavefront .obj text (``v x y z`` lines -- ``v x y z r g b`` when
+        ``vertex_colors`` is set -- then 1-based ``f a b c``); written to ``file_obj``
+        (an open text file or a path) when given."""
         if file_type != "obj":
             raise ValueError(f"Mesh.export: only 'obj' is supported, not {file_type!r}")
-        lines = ["v %.8f %.8f %.8f" % tuple(v) for v in self.vertices.tolist()]
+        if self.vertex_colors is None:
+            lines = ["v %.8f %.8f %.8f" % tuple(v) for v in self.vertices.tolist()]
+        else:
+            if self.vertex_colors.shape != self.vertices.shape:
+                raise ValueError("Mesh.export: vertex_colors must be [V, 3] like vertices")
+            lines = ["v %.8f %.8f %.8f %.6f %.6f %.6f" % tuple(v + c) for v, c in
+                     zip(self.vertices.tolist(), self.vertex_colors.tolist())]
         lines += ["f %d %d %d" % tuple(f) for f in (self.faces + 1).tolist()]
         text = "\n".join(lines) + "\n"
         if file_obj is None:
@@ -127,6 +142,55 @@ def extract_mesh_with_marching_cubes(sdf: torch.Tensor) -> Mesh:
     verts[:, 2] *= -1
     verts[:, 1] *= -1
     return Mesh(verts.cpu().numpy(), faces.cpu().numpy())
+
+
+def cube_points(res: int, device=None) -> torch.Tensor:
+    """Network coordinates [res, res, res, 3] of the cube ``extract_mesh_with_marching_cubes``
+    reads: layout [H (iy), W (ix), D (iz)], and with c(i) = 2 i / res - 1 the point of
+    index (iy, ix, iz) is (c(ix), -c(iy), -c(iz)) -- the network coordinate
+    (``world_to_network``) of the world position that function gives index (ix, iy, iz):
+    (i / res - 0.5) * 0.24 per axis, y and z negated."""
+    c = torch.arange(res, dtype=torch.float32, device=device) * 2 / res - 1
+    yy, xx, zz = torch.meshgrid(-c, c, -c, indexing="ij")
+    return torch.stack([xx, yy, zz], -1)
+
+
+def world_to_network(v, near: float = 0.88, far: float = 1.12):
+    """World position -> what the field network receives under z-normalisation
+    (normalized_pts = pts * 2 / (far - near), sdf_model.py:349)."""
+    return v * 2 / (far - near)
+
+
+def sdf_cube(renderer, styles: torch.Tensor, res: int = 128) -> torch.Tensor:
+    """The SDF of the field itself on ``cube_points(res)``: [B, res, res, res, 1], which
+    goes straight into ``extract_mesh_with_marching_cubes`` (one face at a time) --
+    where sdf_mesh.py renders a res^2 x res frustum with return_sdf and resamples it
+    trilinearly onto the cube (``align_volume``).  ``styles`` [B, 256]: the renderer's
+    latent."""
+    B = styles.shape[0]
+    pts = cube_points(res, styles.device).reshape(1, res ** 3, 3).expand(B, res ** 3, 3)
+    sdf, _ = renderer.query(pts, styles, return_rgb=False)
+    return sdf.reshape(B, res, res, res, 1)
+
+
+def color_mesh(mesh: Mesh, renderer, styles: torch.Tensor, viewdir=(0.0, 0.0, -1.0),
+               near: float = 0.88, far: float = 1.12) -> np.ndarray:
+    """The field's colour at every vertex of ``mesh`` (world coordinates, as
+    ``extract_mesh_with_marching_cubes`` returns them) for the face ``styles`` [1, 256],
+    seen from ``viewdir``: one unit direction, or [V, 3] one per vertex (as the network
+    sees it; not normalised here).  Sets and returns ``mesh.vertex_colors`` [V, 3] in
+    [0, 1]."""
+    if styles.shape[0] != 1:
+        raise ValueError("color_mesh: one mesh, one face (styles [1, 256])")
+    dev = styles.device
+    pts = world_to_network(torch.as_tensor(mesh.vertices, dtype=torch.float32, device=dev),
+                           near, far).unsqueeze(0)
+    vd = torch.as_tensor(np.asarray(viewdir, np.float32), device=dev)
+    vd = vd.reshape(1, 3) if vd.dim() == 1 else vd.reshape(1, -1, 3)
+    with torch.no_grad():
+        _, rgb = renderer.query(pts, styles, viewdirs=vd)
+    mesh.vertex_colors = rgb[0].float().cpu().numpy()
+    return mesh.vertex_colors
 
 
 def xyz2mesh(xyz: torch.Tensor):

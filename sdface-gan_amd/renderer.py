@@ -691,6 +691,116 @@ class VolumeFeatureRenderer(nn.Module):
         self._pack_cache = (key, buf)
         return buf
 
+    # ---------------------------------------------------------------- point query
+    # Points per library call of the fused query.  The workspace is about 144 bytes per
+    # point (the 32 gathered features, the grid coordinate) plus 0.9 MB, so 2^20 points
+    # bound it at ~152 MB; at 32 points per group that is 512 workgroups, two per CU.
+    QUERY_CHUNK_POINTS = 1 << 20
+
+    def _query_fused_ok(self, points, styles):
+        """The rule of ``_fused_ok`` for a point query (the fused query exists for the
+        ngp network on the f16x3 field kernel only)."""
+        if not self.use_fused or self._net_kind() != 0 or self.field_precision != "f16x3":
+            return False
+        if not points.is_cuda or styles.dim() != 2 or styles.shape[1] != 256 \
+                or self.network.W != 256:
+            return False
+        if torch.is_grad_enabled() and (styles.requires_grad or points.requires_grad or any(
+                p.requires_grad for p in self.parameters())):
+            return False
+        return True
+
+    def query(self, points, styles, viewdirs=None, return_rgb=True, chunk_groups=None):
+        """The field itself at arbitrary points: ``(sdf [B,M], rgb [B,M,3] | None)``.
+
+        ``points`` [B,M,3] are NETWORK coordinates (what ``self.network`` receives: a
+        world position times ``2 / (far - near)`` under z-normalisation, see
+        ``mesh.world_to_network``).  ``sdf`` is sigma_linear's output, ``rgb`` is
+        sigmoid(rgb_linear) in [0,1] -- the per-sample values the render composites.
+        ``viewdirs`` is the view direction as the network sees it (unit length; it is
+        not normalised here): ``[B,3]`` one per face, ``[B,M,3]`` one per point, or
+        ``None`` with ``return_rgb=False`` (zeros are passed).
+
+        For an ngp network, CUDA tensors, ``field_precision == 'f16x3'`` and no grad
+        needed this runs ``sdfr_query_ngp_forward``: the render's hash-grid gather and
+        split-fp16 field kernel on the given points.  Per-face (or no) directions run in
+        groups of N = 32 points (M padded, the padding trimmed); per-point directions
+        run as M groups of N = 1, which idles the kernel's odd-sample lanes (it takes
+        kRSamples = 2 points of a group per pass), i.e. half rate.  Calls are chunked
+        over groups (``chunk_groups``, default ``QUERY_CHUNK_POINTS`` / N) to bound the
+        workspace; chunking does not change a bit of the result.  Otherwise (SIREN, FC,
+        CPU tensors, the fp32 field, a call under grad) it runs
+        ``self.network(cat([points, dirs]), styles)``, the autograd path, and slices it.
+        """
+        if points.dim() != 3 or points.shape[-1] != 3:
+            raise ValueError(f"query: points must be [B,M,3], got {tuple(points.shape)}")
+        B, M = points.shape[:2]
+        if viewdirs is None:
+            if return_rgb:
+                raise ValueError("query: return_rgb needs viewdirs")
+            viewdirs = points.new_zeros(B, 3)
+        per_point = viewdirs.dim() == 3
+        if tuple(viewdirs.shape) != ((B, M, 3) if per_point else (B, 3)):
+            raise ValueError(f"query: viewdirs must be [B,3] or [B,M,3] for points "
+                             f"{tuple(points.shape)}, got {tuple(viewdirs.shape)}")
+        if not self._query_fused_ok(points, styles):
+            dirs = viewdirs if per_point else viewdirs.unsqueeze(1).expand(B, M, 3)
+            raw = self.network(torch.cat([points, dirs.to(points)], -1), styles=styles)
+            return raw[..., 3], (torch.sigmoid(raw[..., :3]) if return_rgb else None)
+        # groups of N points sharing a direction: [B,R,N,3] points, [B,R,3] directions
+        N = 1 if per_point else 32
+        R = (M + N - 1) // N
+        pts = points.detach().float()
+        if R * N != M:
+            pts = torch.cat([pts, pts.new_zeros(B, R * N - M, 3)], 1)
+        dirs = viewdirs.detach().to(device=points.device, dtype=torch.float32)
+        dirs = dirs if per_point else dirs.unsqueeze(1).expand(B, R, 3)
+        sdf, rgb = self._fused_query(pts.reshape(B, R, N, 3), dirs, styles, return_rgb,
+                                     chunk_groups)
+        sdf = sdf.reshape(B, R * N)[:, :M]
+        return sdf, (rgb.reshape(B, R * N, 3)[:, :M] if return_rgb else None)
+
+    def _fused_query(self, points, dirs, styles, return_rgb=True, chunk_groups=None):
+        """``sdfr_query_ngp_forward`` on grouped points: ``points`` [B,R,N,3], ``dirs``
+        [B,R,3] (one per group) -> (sdf [B,R,N], rgb [B,R,N,3] | None), in calls of at
+        most ``chunk_groups`` groups per face."""
+        self._fused_check_params()
+        dev = points.device
+        B, R, N = points.shape[:3]
+        pts = points.detach().float().contiguous()
+        styles = styles.detach().float().contiguous()
+        sdf = torch.empty(B, R, N, device=dev)
+        rgb = torch.empty(B, R, N, 3, device=dev) if return_rgb else None
+        if chunk_groups is None:
+            chunk_groups = max(16, self.QUERY_CHUNK_POINTS // (B * N) // 16 * 16)
+        L = _lib.lib()
+        prepacked = self._prepacked(0, pts)
+        w = self._weight_struct(0)
+        whole = R <= chunk_groups
+        ws = None
+        for r0 in range(0, R, chunk_groups):
+            r1 = min(R, r0 + chunk_groups)
+            # a chunk is a call of its own on contiguous [B,r,..] tensors
+            c_pts = pts if whole else pts[:, r0:r1].contiguous()
+            c_dirs = dirs[:, r0:r1].float().contiguous()
+            c_sdf = sdf if whole else torch.empty(B, r1 - r0, N, device=dev)
+            c_rgb = rgb if whole or rgb is None else torch.empty(B, r1 - r0, N, 3, device=dev)
+            need = L.sdfr_query_ngp_workspace_bytes(B, r1 - r0, N)
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            a = _lib.NgpQueryArgs(
+                B=B, R=r1 - r0, N=N, points=_lib.ptr(c_pts), dirs=_lib.ptr(c_dirs),
+                styles=_lib.ptr(styles), sdf=_lib.ptr(c_sdf), rgb=_lib.ptr(c_rgb),
+                workspace=_lib.ptr(ws), workspace_bytes=ws.numel(),
+                prepacked=_lib.ptr(prepacked))
+            _lib.check(L.sdfr_query_ngp_forward(ctypes.byref(w), ctypes.byref(a),
+                                                _lib.stream_of(pts)), "sdfr_query_ngp_forward")
+            if not whole:
+                sdf[:, r0:r1] = c_sdf
+                if rgb is not None:
+                    rgb[:, r0:r1] = c_rgb
+        return sdf, rgb
+
     # ---------------------------------------------------------------- API
     def forward(self, cam_poses, focal, near, far, styles=None, return_eikonal=False,
                 t_rand=None, styles_event=None, feat_mod=None):
