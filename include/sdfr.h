@@ -42,7 +42,7 @@ extern "C" {
 #define SDFR_ELAUNCH (-2)      /* HIP launch or runtime error                 */
 #define SDFR_EUNSUPPORTED (-3) /* valid for the reference, not implemented    */
 
-#define SDFR_ABI_VERSION 14
+#define SDFR_ABI_VERSION 15
 
 int sdfr_abi_version(void);
 /* Thread-local message for the last non-zero status of this thread. */
@@ -311,6 +311,40 @@ typedef struct sdfr_ngp_query_args {
 } sdfr_ngp_query_args;
 size_t sdfr_query_ngp_workspace_bytes(uint32_t B, uint32_t R, uint32_t N);
 int sdfr_query_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_query_args *a, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Fused SDF and its exact gradient at caller-supplied points (ABI 15; replaces autograd
+ * through NGPSIRENGenerator's SDF trunk, as get_eikonal_term uses it, sdf_model.py:224-229).
+ * A gather that stores, per point, the 32 hash-grid features and their derivatives with
+ * respect to the grid coordinate (the values and dy_dx of sdfr_grid_encode_forward, bit
+ * for bit), then a forward-mode split-fp16 field kernel over the SDF trunk (composed
+ * layer 0, pts_linears.1-2, sigma_linear; no views layer, no colour): the value and its
+ * three tangents are four MFMA columns of the query's GEMM stream on the same packed
+ * weights (their first 34 slices) and FiLM vectors.  sdf is the query's SDF bit for bit;
+ * grad is d sdf / d point in NETWORK coordinates (the coordinates of `points`).  A point
+ * whose grid coordinate leaves [0,1] in any axis has zero features and a zero gradient.
+ * The hash grid is piecewise trilinear: on a cell face the gradient is that of the cell
+ * the gather's floor() selects.
+ * Workspace: 512 bytes per padded point (M rounded up to 8 per face; the region starts
+ * with the gather's output [B][Mp][4 = value, d/du_0..2][32] fp32) + 8 KiB of FiLM vectors
+ * per face + the weight-packing region.  SDFR_EINVAL before any launch for null
+ * arguments or required pointers, zero sizes, a workspace below
+ * sdfr_query_ngp_grad_workspace_bytes(B, M), or 2^25 or more padded points in one call
+ * (the kernels index the gather's output in fp32 elements, 128 per padded point, with
+ * 32-bit arithmetic; sdfr_query_ngp_grad_workspace_bytes returns 0 for such a size);
+ * SDFR_EUNSUPPORTED for num_levels != 16.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfr_ngp_grad_args {
+    uint32_t B, M;            /* faces; points per face                        */
+    const float *points;      /* [B,M,3] network coordinates                   */
+    const float *styles;      /* [B,256]                                       */
+    float *sdf;               /* [B,M] or NULL                                 */
+    float *grad;              /* [B,M,3] d sdf / d point (network coordinates) */
+    void *workspace; size_t workspace_bytes;
+    const void *prepacked;    /* as sdfr_ngp_query_args.prepacked, or NULL     */
+} sdfr_ngp_grad_args;
+size_t sdfr_query_ngp_grad_workspace_bytes(uint32_t B, uint32_t M);
+int sdfr_query_ngp_grad(const sdfr_ngp_weights *w, const sdfr_ngp_grad_args *a, void *stream);
 
 #ifdef SDFR_ABLATION
 /* Profiling hooks, exported only by `make ABLATION=1` builds (lib_abl/libsdfr.so,

@@ -13,7 +13,10 @@ Drop-in surface (reference: im2scene/sdf/models/):
   HIP, csrc/mesh.hip), xyz2mesh                       (sdf_utils.py:164-223)
 Beyond the reference: VolumeFeatureRenderer.query / Generator.query_field (the field at
 arbitrary points, fused: sdfr_query_ngp_forward), cube_points, sdf_cube, world_to_network,
-color_mesh (meshes from the field itself, vertex colours).
+color_mesh (meshes from the field itself, vertex colours);
+VolumeFeatureRenderer.query_gradient / Generator.query_field_gradient (the SDF's exact
+gradient, fused: sdfr_query_ngp_grad), normal_mesh, eikonal_residual (vertex normals, the
+eikonal check).
   SDFOptions, vol_render_opt                            (sdf_utils.py:447, training_utils.py:144)
 Beyond the reference: GraphedGenerator (HIP-graph replay of the inference forward).
 """
@@ -26,8 +29,8 @@ from .generator import (Blur, Decoder, EqualLinear, FusedLeakyReLU, Generator,  
                         ToRGB, Upsample, fused_leaky_relu, make_kernel, upfirdn2d)
 from .graphs import GraphedGenerator  # noqa: F401
 from .mesh import (Mesh, align_volume, color_mesh, cube_points,  # noqa: F401
-                   extract_mesh_with_marching_cubes, marching_cubes, sdf_cube,
-                   world_to_network, xyz2mesh)
+                   eikonal_residual, extract_mesh_with_marching_cubes, marching_cubes,
+                   normal_mesh, sdf_cube, world_to_network, xyz2mesh)
 from .options import AttrDict, SDFOptions, vol_render_opt  # noqa: F401
 from . import training  # noqa: F401  (stage-2 DDP trainer, Discriminator, losses)
 from .renderer import (FCGenerator, FiLMSiren, LinearLayer, NGPSIRENGenerator,  # noqa: F401

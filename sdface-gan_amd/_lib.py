@@ -23,7 +23,7 @@ SDFR_OK = 0
 SDFR_EINVAL = -1
 SDFR_ELAUNCH = -2
 SDFR_EUNSUPPORTED = -3
-ABI_VERSION = 14
+ABI_VERSION = 15
 FIELD_F16X3 = 0
 FIELD_FP32 = 1
 
@@ -37,6 +37,7 @@ EXPORTS = (
     "sdfr_sh_encode_forward", "sdfr_sh_encode_backward",
     "sdfr_render_ngp_workspace_bytes", "sdfr_render_ngp_forward",
     "sdfr_render_ngp_encode_only", "sdfr_query_ngp_workspace_bytes", "sdfr_query_ngp_forward",
+    "sdfr_query_ngp_grad_workspace_bytes", "sdfr_query_ngp_grad",
     "sdfr_debug_sin_probe",
     "sdfr_debug_sin_rev_probe", "sdfr_camera_extrinsics",
     "sdfr_render_siren_workspace_bytes", "sdfr_render_siren_forward",
@@ -119,6 +120,15 @@ class NgpQueryArgs(ctypes.Structure):
     _fields_ = [
         ("B", _u32), ("R", _u32), ("N", _u32),
         ("points", _vp), ("dirs", _vp), ("styles", _vp), ("sdf", _vp), ("rgb", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("prepacked", _vp),
+    ]
+
+
+class NgpGradArgs(ctypes.Structure):
+    """sdfr_ngp_grad_args (include/sdfr.h, ABI 15)."""
+    _fields_ = [
+        ("B", _u32), ("M", _u32),
+        ("points", _vp), ("styles", _vp), ("sdf", _vp), ("grad", _vp),
         ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("prepacked", _vp),
     ]
 
@@ -206,6 +216,10 @@ def lib():
     L.sdfr_query_ngp_workspace_bytes.argtypes = [_u32, _u32, _u32]
     L.sdfr_query_ngp_forward.argtypes = [ctypes.POINTER(NgpWeights),
                                          ctypes.POINTER(NgpQueryArgs), _vp]
+    L.sdfr_query_ngp_grad_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_query_ngp_grad_workspace_bytes.argtypes = [_u32, _u32]
+    L.sdfr_query_ngp_grad.argtypes = [ctypes.POINTER(NgpWeights),
+                                      ctypes.POINTER(NgpGradArgs), _vp]
     for name in ABLATION_EXPORTS:           # profiling builds only (make ABLATION=1)
         if hasattr(L, name):
             getattr(L, name).argtypes = [_int]

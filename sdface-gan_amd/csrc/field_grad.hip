@@ -1,0 +1,437 @@
+// field_grad.hip -- the fused ngp SDF and its exact gradient at caller-supplied points
+// (sdfr_query_ngp_grad, host side in render_ngp.hip):
+//
+//   ngp_encode_grad_kernel   points [B,M,3] -> gd: per point the 32 hash-grid features and
+//                            their 3 x 32 derivatives with respect to the grid coordinate u
+//   field_g_kernel           forward-mode derivative of the SDF trunk (composed layer 0,
+//                            pts_linears.1-2, sigma_linear) on split-fp16 MFMA: the value and
+//                            its three tangents are four MFMA columns of one GEMM stream
+//
+// Gather layout (gd): [B Mp][4 kinds][32] fp32, Mp = M rounded up to 8 (one wave pass);
+// kind 0 holds the features (feature 2 level + c), kind 1 + k their derivatives d/du_k.
+// 512 B per padded point; padding points and points outside [0,1]^3 hold zeros.  One
+// column of the field kernel (point, kind) reads its 32 inputs as 128 contiguous bytes:
+// lane half h of k-step st takes floats 16 st + 8 h .. + 7 (two 16-B loads), so the eight
+// lanes of a point read its 512 B once.  The kernels index gd in fp32 elements with 32-bit
+// arithmetic (128 per padded point), hence the call limit B Mp < 2^25.
+//
+// The value uses the rounded operations of level_interp (bit-identical to
+// ngp_encode_kernel's features), the derivatives those of grid_fwd_kernel's dy_dx
+// (gridencoder.cu:201-244) on the same 8 corner rows (level_value / level_dy_dx,
+// sdfr_common.h): both are bit-identical to sdfr_grid_encode_forward(..., calc_dy_dx) at
+// the same u, and u is formed with query_geom_kernel's three rounded ops.
+//
+// Field kernel: the k-step loop, the LDS-DMA weight ring and the in-register hand-off of
+// activated accumulators as the next layer's B fragments are field_r_kernel's (rstep,
+// field_f16x3.hip), run on the first 2 + 32 slices of the same packed weights with the same
+// FiLM vectors.  A wave's 32 MFMA columns are 8 points x {value, d/du_0, d/du_1, d/du_2},
+// a point's four columns in adjacent lanes (column c = 4 point + kind).  Per accumulator
+// register, with z the GEMM output of the lane's own column and u = fma(gamma'', z_value,
+// beta'') (revolutions) fetched from the quad's value lane by a quad-broadcast DPP move:
+//     value lane     sin_rev(u)                       (field_r_kernel's arithmetic, bit for bit)
+//     tangent lane   cos_rev(u) (2 pi gamma'') z      (no bias: it is folded into beta'')
+// Tangents are unbounded, and the hi/lo fp16 split is fp32-accurate only inside fp16's
+// range, so every tangent column is rescaled by a power of two before each split: after a
+// layer's GEMM the column maximum m of |2 pi gamma'' z| over its 256 rows (an upper bound
+// of the activated tangent, |cos| <= 1) gives 2^-ex(m), which brings the column into
+// [-1, 1]; the cumulative exponent is carried per lane and undone exactly on the final
+// sum.  The layer-0 inputs (features / derivative columns) are scaled the same way
+// (field_r_kernel's es).  An all-zero column (a point outside the box) keeps exponent 0.
+// The last layer's tangents feed fp32 fmas only and are not rescaled.
+//
+// This unit includes field_f16x3.hip for its templates and helpers alone
+// (SDFR_FIELD_QUERY_TU leaves out its non-template kernels and host code) and instantiates
+// nothing of the render's; it is built with the field kernels' flags.
+#define SDFR_FIELD_QUERY_TU 1
+#include "field_f16x3.hip"
+
+namespace sdfr {
+
+constexpr uint32_t kGPts = kGradPts;             // points per wave pass (32 columns / 4 kinds)
+constexpr uint32_t kGGroup = kGPts * kRWaves;    // points per workgroup pass
+constexpr uint32_t kGPointF = 4 * kFeatIn;       // fp32 elements of gd per padded point
+static_assert(kGPts == 8 && kGPointF * sizeof(float) == kGradPointBytes, "gather layout");
+
+// ----------------------------------------------------------------------------
+// gather with input derivatives
+// ----------------------------------------------------------------------------
+struct GGatherArgs {
+    const float *points;           // [B,M,3] network coordinates
+    const float *emb;
+    const int32_t *offsets;
+    float *gd;                     // [B Mp][4][32]
+    LevelTable lt;
+    uint32_t M, Mp, P;             // P = B Mp padded points
+    float bound;
+    int pair_ok;                   // table 16-B aligned (paired corner loads)
+};
+
+// One thread per (padded point, level), level fastest: the 16 lanes of a point store 128
+// contiguous bytes per kind.
+__global__ void __launch_bounds__(256) ngp_encode_grad_kernel(const GGatherArgs a) {
+    __shared__ LevelParam lp[16];
+    if (threadIdx.x < 16) {
+        LevelParam q = a.lt.p[threadIdx.x];
+        finish_level(q, a.offsets, threadIdx.x, 3, 0, 0);
+        lp[threadIdx.x] = q;
+    }
+    __syncthreads();
+    const uint32_t level = threadIdx.x & 15u;
+    const uint32_t pid = blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (pid >= a.P) return;
+    const uint32_t b = pid / a.Mp, m = pid % a.Mp;
+    float2 *out = reinterpret_cast<float2 *>(a.gd + pid * kGPointF) + level;
+    bool in = m < a.M;
+    float u[3] = {0.5f, 0.5f, 0.5f};
+    if (in) {
+        const float *p = a.points + ((size_t)b * a.M + m) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            u[k] = __fdiv_rn(__fadd_rn(p[k], a.bound), __fmul_rn(2.0f, a.bound));   // grid.py:149
+            if (u[k] < 0 || u[k] > 1) in = false;
+        }
+    }
+    if (!in) {
+#pragma unroll
+        for (int kind = 0; kind < 4; ++kind) out[kind * 16] = make_float2(0.0f, 0.0f);
+        return;
+    }
+    const LevelParam q = lp[level];
+    const float *grid = a.emb + (size_t)q.offset * 2;
+    LevelCoord<3, 2> lc;
+    level_coord<3, 2>(u, q, 0, 0, lc);
+    float v[8][2];
+    if (a.pair_ok && !((q.offset | q.hsize) & 1u))
+        level_corners<3, 2, true>(grid, q, 0, lc, v);
+    else
+        level_corners<3, 2, false>(grid, q, 0, lc, v);
+    // value and derivatives from the same corner rows
+    float res[2];
+    level_value<3, 2>(lc, v, res);
+    out[0] = make_float2(res[0], res[1]);
+#pragma unroll
+    for (uint32_t gd = 0; gd < 3; ++gd) {
+        float rg[2];
+        level_dy_dx<3, 2>(lc, q.scale, v, gd, rg);
+        out[(1 + gd) * 16] = make_float2(rg[0], rg[1]);
+    }
+}
+
+// ----------------------------------------------------------------------------
+// gradient field kernel
+// ----------------------------------------------------------------------------
+// The SDF trunk of NgpNet: layer 0 (2 k-steps) and two dense layers (16 each) = the first
+// 34 slices of NgpNet's packing; no views layer.
+struct NgpGradNet {
+    static constexpr int kL0 = 2;
+    static constexpr int kHidden = 2;
+    static constexpr int kViewSteps = 0;
+    static constexpr bool kFieldR = true;
+    static constexpr int kFilmN = 3;             // pts_linears.0-2
+    static constexpr uint32_t kSlices = 2 + 16 * 2;
+};
+
+struct GFieldArgs {
+    const float *gd;               // [B Mp][4][32]
+    const f4 *packed;              // NgpNet's packed weights (first 34 slices read)
+    const float *film;             // [B][kFilm = 4][2][256] (xprep_kernel<NgpNet>)
+    const float *sigma_w, *sigma_b;
+    float *sdf;                    // [B,M] or null
+    float *grad;                   // [B,M,3]
+    uint32_t M, Mp, wg_per_face;
+    float bound;
+};
+
+__device__ __forceinline__ float quad_bcast0(float v) {   // lane n <- lane n & ~3
+    return __builtin_bit_cast(
+        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x00, 0xF, 0xF, false));
+}
+
+// power-of-two exponent of a column maximum: m = f 2^ex, f in [0.5, 1); 0 for an all-zero
+// or non-finite column
+__device__ __forceinline__ int col_exp(float m) {
+    if (!(m > 0.0f && m < 3.0e38f)) return 0;
+    const int ex = __builtin_amdgcn_frexp_expf(m);
+    return ex < -120 ? -120 : ex;
+}
+
+// One activated register.  MODE 0: layer 0 (the value's feature scale 2^es undone as in
+// r_act), 1: a dense layer, 2: the last layer (+ the sigma head's partial dot product).
+// ex: the tangent column's rescale exponent for this layer's output.
+template <int MODE>
+__device__ __forceinline__ float g_act1(float zz, float g, float b, float w, bool tangent, int es,
+                                        int ex, float &sdfp) {
+    constexpr float k2pi = 6.28318530717958647692f;
+    const float uo = MODE == 0 ? __fmaf_rn(g, __builtin_ldexpf(zz, -es), b) : __fmaf_rn(g, zz, b);
+    const float u = quad_bcast0(uo);
+    const float sv = sin_rev(u);
+    const float cv = __builtin_amdgcn_cosf(u);
+    const float tv = __builtin_ldexpf(__fmul_rn(__fmul_rn(cv, __fmul_rn(k2pi, g)), zz), -ex);
+    const float v = tangent ? tv : sv;
+    if constexpr (MODE == 2) sdfp = __fmaf_rn(v, w, sdfp);
+    return v;
+}
+
+__global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs a) {
+    using Net = NgpGradNet;
+    constexpr int NF = Net::kFilmN;
+    constexpr int KL0 = Net::kL0;
+    constexpr int NS = RNet<Net>::kSteps;
+    static_assert(NS == 34 && (NS & 1) == 0, "the SDF trunk's k-steps");
+    __shared__ f4 ring_lds[4 * kRSliceF4];                  // 64 KB weight ring
+    __shared__ float film_lds[NF * 2 * kW];                 // the workgroup's face
+    __shared__ float cst[kW];                               // sigma_w
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t c = lane & 31u, h = lane >> 5;
+    const uint32_t kind = c & 3u, pt8 = c >> 2;
+    const bool tangent = kind != 0u;
+    const uint32_t b = blockIdx.x / a.wg_per_face, wg = blockIdx.x % a.wg_per_face;
+    {
+        const f4 *src = reinterpret_cast<const f4 *>(a.film + (size_t)b * kFilm * 2 * kW);
+        f4 *dst = reinterpret_cast<f4 *>(film_lds);
+        for (uint32_t i = tid; i < NF * 2 * kW / 4; i += kRThreads) dst[i] = src[i];
+    }
+    RRing R;
+    R.lds = ring_lds;
+    R.tid = tid;
+    R.wave = wave;
+    R.ubase = 0;
+    R.drsrc = make_rsrc(a.packed, Net::kSlices * kXSliceF4 * sizeof(f4));
+    for (uint32_t i = tid; i < kW; i += kRThreads) cst[i] = a.sigma_w[i];
+    // prologue: units 0, 1 (slices 0-3) -> slots 0-3 (unit U's barrier issues unit U + 2)
+    r_dma<0>(R, 0);
+    r_dma<1>(R, 1);
+    r_dma<2>(R, 2);
+    r_dma<3>(R, 3);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    const float *sig_w = cst;
+    auto fg = [&](int f) { return (const float *)film_lds + f * 2 * kW; };
+    auto fb = [&](int f) { return (const float *)film_lds + f * 2 * kW + kW; };
+    const float sig_b = a.sigma_b[0];
+    const uint32_t npass = a.Mp / kGGroup + (a.Mp % kGGroup ? 1u : 0u);
+
+    f4 ld[4];                                               // [layer-0 k-step][16-B half]
+    // this lane's point of pass p: clamped into the face for the loads
+    auto point_of = [&](uint32_t p) { return (p * kRWaves + wave) * kGPts + pt8; };
+    auto load_inputs = [&](uint32_t p) {
+        uint32_t m = point_of(p);
+        if (m >= a.M) m = a.M - 1;
+        const float *src = a.gd + ((b * a.Mp + m) * 4u + kind) * kFeatIn + 8u * h;
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            ld[2 * st] = *reinterpret_cast<const f4 *>(src + 16 * st);
+            ld[2 * st + 1] = *reinterpret_cast<const f4 *>(src + 16 * st + 4);
+        }
+    };
+    load_inputs(wg);
+
+    uint32_t it = 0;
+    for (uint32_t p = wg; p < npass; p += a.wg_per_face, ++it) {
+        R.ubase = __builtin_amdgcn_readfirstlane((it * (uint32_t)(NS / 2)) & 1u);
+        r_na(R, r_slot<Net>(R, 0));
+        f16v X[8], Y[8];
+        f4 bf[2], bn[2], E[KL0][2];
+        int es = 0;                                         // the column's layer-0 input scale
+        {
+            float v[16];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[4 * k + r] = ld[k][r];
+            // the column's 32 inputs over both lane halves -> 2^es into [0.5, 1)
+            float m = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) m = fmaxf(m, fabsf(v[j]));
+            m = fmaxf(m, __shfl_xor(m, 32));
+            if (m > 0.0f && m < 3.0e38f) {
+                const int ex = __builtin_amdgcn_frexp_expf(m);
+                es = ex < -100 ? 100 : -ex;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) v[j] = __builtin_ldexpf(v[j], es);
+            }
+            float u0[8], u1[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                u0[j] = v[j];
+                u1[j] = v[8 + j];
+            }
+            split8(u0, E[0][0], E[0][1]);
+            split8(u1, E[1][0], E[1][1]);
+        }
+        int ts = es;                                        // tangent: cumulative scale exponent
+        float sdfp = 0.0f;
+        struct ActState {
+            f4 gm0, bt0, w0, gm1, bt1, w1;
+            float v[8];
+        };
+        ActState as;
+        auto film_load = [&](auto L, int q) {
+            constexpr int l = decltype(L)::value;
+            const int r0 = 32 * (q >> 1) + 16 * (q & 1) + 4 * (int)h;
+            as.gm0 = *reinterpret_cast<const f4 *>(fg(l) + r0);
+            as.gm1 = *reinterpret_cast<const f4 *>(fg(l) + r0 + 8);
+            as.bt0 = *reinterpret_cast<const f4 *>(fb(l) + r0);
+            as.bt1 = *reinterpret_cast<const f4 *>(fb(l) + r0 + 8);
+            if constexpr (l == 2) {
+                as.w0 = *reinterpret_cast<const f4 *>(sig_w + r0);
+                as.w1 = *reinterpret_cast<const f4 *>(sig_w + r0 + 8);
+            }
+        };
+        // register j of chunk q (registers 8 (q & 1) .. + 7 of tile q >> 1) of layer l's output
+        auto act_reg = [&](auto L, f16v (&o)[8], int q, int j, int ex) {
+            constexpr int l = decltype(L)::value;
+            const float g = j < 4 ? as.gm0[j & 3] : as.gm1[j & 3];
+            const float bb = j < 4 ? as.bt0[j & 3] : as.bt1[j & 3];
+            const float w = l == 2 ? (j < 4 ? as.w0[j & 3] : as.w1[j & 3]) : 0.0f;
+            as.v[j] = g_act1<l>(o[q >> 1][8 * (q & 1) + j], g, bb, w, tangent, es, ex, sdfp);
+        };
+        // activation of chunk q into bn spread over a k-step's groups: film vectors read
+        // beside group 0, one register beside each of groups 1-5, two beside group 6, the
+        // last and the split beside group 7 (the VALU slots a 32x32 MFMA leaves free)
+        auto act_side = [&](auto L, f16v (&o)[8], int q, auto GI, int ex) {
+            constexpr int gi = decltype(GI)::value;
+            if constexpr (gi == 0) {
+                film_load(L, q);
+            } else if constexpr (gi <= 5) {
+                act_reg(L, o, q, gi - 1, ex);
+            } else if constexpr (gi == 6) {
+                act_reg(L, o, q, 5, ex);
+                act_reg(L, o, q, 6, ex);
+            } else {
+                act_reg(L, o, q, 7, ex);
+                split8(as.v, bn[0], bn[1]);
+            }
+        };
+        auto act_now = [&](auto L, f16v (&o)[8], int q, int ex) {
+            film_load(L, q);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) act_reg(L, o, q, j, ex);
+        };
+        // the tangent columns' rescale exponent for layer l's output o: the maximum of
+        // |2 pi gamma'' z| over the column's 256 rows (register v of tile T: row
+        // 32 T + (v & 3) + 8 (v >> 2) + 4 h), 0 in value lanes
+        auto col_scale = [&](auto L, f16v (&o)[8]) {
+            constexpr int l = decltype(L)::value;
+            float m = 0.0f;
+#pragma unroll
+            for (int T = 0; T < 8; ++T)
+#pragma unroll
+                for (int bq = 0; bq < 4; ++bq) {
+                    const f4 gm = *reinterpret_cast<const f4 *>(fg(l) + 32 * T + 8 * bq + 4 * (int)h);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(__fmul_rn(gm[r], o[T][4 * bq + r])));
+                }
+            m = fmaxf(m, __shfl_xor(m, 32));
+            const int ex = col_exp(__fmul_rn(m, 6.28318530717958647692f));
+            return tangent ? ex : 0;
+        };
+        constexpr std::integral_constant<int, 0> L0{};
+        constexpr std::integral_constant<int, 1> L1{};
+        constexpr std::integral_constant<int, 2> L2{};
+        // layer 0: K = 32, 2 k-steps
+        sfor<0, KL0>([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            bf[0] = E[j][0];
+            bf[1] = E[j][1];
+            rstep<Net, j, j == 0>(R, X, bf, [&](auto) {});
+        });
+        int ex = col_scale(L0, X);
+        ts -= ex;
+        act_now(L0, X, 0, ex);
+        split8(as.v, bn[0], bn[1]);
+        // dense layer 1: X -> Y, activating layer 0's chunks one k-step ahead
+        sfor<0, 16>([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            bf[0] = bn[0];
+            bf[1] = bn[1];
+            rstep<Net, KL0 + j, j == 0>(R, Y, bf, [&](auto GI) {
+                if constexpr (j < 15) act_side(L0, X, j + 1, GI, ex);
+            });
+        });
+        ex = col_scale(L1, Y);
+        ts -= ex;
+        act_now(L1, Y, 0, ex);
+        split8(as.v, bn[0], bn[1]);
+        // dense layer 2: Y -> X; the next pass's inputs are loaded under its last k-steps
+        const bool more = p + a.wg_per_face < npass;
+        sfor<0, 16>([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            bf[0] = bn[0];
+            bf[1] = bn[1];
+            if constexpr (j == 12) {
+                if (more) load_inputs(p + a.wg_per_face);
+            }
+            rstep<Net, KL0 + 16 + j, j == 0>(R, X, bf, [&](auto GI) {
+                if constexpr (j < 15) act_side(L1, Y, j + 1, GI, ex);
+            });
+        });
+        // last FiLM layer and sigma_linear: the value column's dot product in
+        // field_r_kernel's order (chunks 0..15, registers 0..7), the tangents' likewise
+        // without the bias
+#pragma unroll
+        for (int q = 0; q < 16; ++q) act_now(L2, X, q, 0);
+        const float tot = __fadd_rn(sdfp, __shfl_xor(sdfp, 32));
+        const uint32_t m = point_of(p);
+        if (h == 0 && m < a.M) {
+            const size_t o = (size_t)b * a.M + m;
+            if (!tangent) {
+                if (a.sdf) a.sdf[o] = __fadd_rn(tot, sig_b);
+            } else {
+                // d sdf / d u_k, then / (2 bound): the derivative of u = (p + bound) / (2 bound)
+                a.grad[o * 3 + (kind - 1u)] =
+                    __fdiv_rn(__builtin_ldexpf(tot, -ts), __fmul_rn(2.0f, a.bound));
+            }
+        }
+    }
+    // the ring runs ahead across passes: no LDS-DMA may land after the workgroup ends
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// ----------------------------------------------------------------------------
+// host
+// ----------------------------------------------------------------------------
+int launch_grad_gather(const sdfr_ngp_weights *w, const float *points, float *gd, uint32_t B,
+                       uint32_t M, uint32_t Mp, hipStream_t st) {
+    GGatherArgs e;
+    e.points = points;
+    e.emb = w->embeddings;
+    e.offsets = w->offsets;
+    e.gd = gd;
+    make_level_table(16, w->log2_per_level_scale, w->base_resolution, e.lt);
+    e.M = M;
+    e.Mp = Mp;
+    e.P = B * Mp;
+    e.bound = w->bound;
+    e.pair_ok = (reinterpret_cast<uintptr_t>(w->embeddings) & 15u) == 0;
+    hipLaunchKernelGGL(ngp_encode_grad_kernel, dim3((e.P + 15) / 16), dim3(256), 0, st, e);
+    return check_launch("query_ngp_grad: gather");
+}
+
+// xws: the packed weights' region (workspace or the caller's prepacked buffer)
+int launch_gfield_ngp(const sdfr_ngp_weights *w, const char *xws, const float *film,
+                      const float *gd, float *sdf, float *grad, uint32_t B, uint32_t M,
+                      uint32_t Mp, hipStream_t st) {
+    GFieldArgs f{};
+    f.gd = gd;
+    f.packed = reinterpret_cast<const f4 *>(xws);
+    f.film = film;
+    f.sigma_w = w->sigma_w;
+    f.sigma_b = w->sigma_b;
+    f.sdf = sdf;
+    f.grad = grad;
+    f.M = M;
+    f.Mp = Mp;
+    f.bound = w->bound;
+    // workgroups of a face take its passes (32 points each) round robin: about four
+    // workgroups per CU over the call, every workgroup at least one pass
+    const uint32_t npass = (Mp + kGGroup - 1) / kGGroup;
+    const uint32_t want = (1024u + B - 1) / B;
+    f.wg_per_face = npass < want ? npass : want;
+    hipLaunchKernelGGL(field_g_kernel, dim3(B * f.wg_per_face), dim3(kRThreads), 0, st, f);
+    return check_launch("query_ngp_grad: field (f16x3)");
+}
+
+}  // namespace sdfr

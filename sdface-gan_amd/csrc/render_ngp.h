@@ -144,6 +144,16 @@ int launch_query_geom(const float *points, f4 *gu, const GeomArgs &g, hipStream_
 int launch_qfield_ngp(const sdfr_ngp_weights *w, const GeomArgs &g, const float *enc,
                       const char *xws, const float *film, float *sdf, float *rgb,
                       hipStream_t st);
+// SDF and gradient at caller points (field_grad.hip): the gather with input derivatives
+// (gd [B Mp][4][32], Mp = M rounded up to kGradPts) and the forward-mode field kernel
+// (xws = the packed weights' region; sdf [B,M] or null, grad [B,M,3]).
+constexpr uint32_t kGradPts = 8;             // points per wave pass: the padding unit of M
+constexpr uint32_t kGradPointBytes = 4 * kFeatIn * sizeof(float);   // gd per padded point
+int launch_grad_gather(const sdfr_ngp_weights *w, const float *points, float *gd, uint32_t B,
+                       uint32_t M, uint32_t Mp, hipStream_t st);
+int launch_gfield_ngp(const sdfr_ngp_weights *w, const char *xws, const float *film,
+                      const float *gd, float *sdf, float *grad, uint32_t B, uint32_t M,
+                      uint32_t Mp, hipStream_t st);
 // sample-segment split of the f16x3 field kernel for small batches
 constexpr uint32_t kFieldSplitMax = 4;   // sample segments per ray at most
 uint32_t field_nseg(uint32_t B, uint32_t tiles_per_face, uint32_t N, int force_background,

@@ -1240,4 +1240,71 @@ int sdfr_query_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_query_args 
     return launch_qfield_ngp(w, g, enc, xws, film, a->sdf, a->rgb, st);
 }
 
+// ----------------------------------------------------------------------------
+// SDF and its gradient at caller points (ABI 15): the gather with input derivatives and
+// the forward-mode f16x3 field kernel on the SDF trunk (kernels: field_grad.hip)
+// ----------------------------------------------------------------------------
+// gd [B Mp][4][32] | film [B][4][2][256] | split-fp16 region; Mp = M rounded up to 8.
+// The kernels index gd in fp32 elements, 128 per padded point, with 32-bit arithmetic:
+// P = B Mp >= 2^25 is too many points for one call (P < 2^64: B < 2^32, Mp <= 2^32), and
+// returns 0 before any byte size is formed.
+constexpr uint64_t kGradMaxPoints = (1ull << 32) / (kGradPointBytes / sizeof(float));
+static size_t grad_ws_layout(uint32_t B, uint32_t M, uint64_t *P_out, size_t *o_film = nullptr,
+                             size_t *o_x = nullptr) {
+    const uint64_t Mp = ((uint64_t)M + kGradPts - 1) / kGradPts * kGradPts;
+    const uint64_t P = (uint64_t)B * Mp;
+    if (P_out) *P_out = P;
+    if (P >= kGradMaxPoints) return 0;
+    size_t off = align256((size_t)P * kGradPointBytes);
+    if (o_film) *o_film = off;
+    off += align256((size_t)B * kFilm * 2 * kW * sizeof(float));
+    if (o_x) *o_x = off;
+    off += align256(f16x3_ws_bytes(0));
+    return off;
+}
+
+size_t sdfr_query_ngp_grad_workspace_bytes(uint32_t B, uint32_t M) {
+    return grad_ws_layout(B, M, nullptr);
+}
+
+int sdfr_query_ngp_grad(const sdfr_ngp_weights *w, const sdfr_ngp_grad_args *a, void *stream) {
+    if (!w || !a) return fail(SDFR_EINVAL, "query_ngp_grad: null args");
+    if (w->num_levels != 16)
+        return fail(SDFR_EUNSUPPORTED, "query_ngp_grad: fused path needs 16 levels x 2 features");
+    if (a->B == 0 || a->M == 0) return fail(SDFR_EINVAL, "query_ngp_grad: empty batch / point count");
+    if (!a->points || !a->styles || !a->grad || !a->workspace)
+        return fail(SDFR_EINVAL, "query_ngp_grad: required pointer is null");
+    const void *need[] = {w->embeddings, w->offsets, w->input_w, w->input_b, w->views_w,
+                          w->views_b, w->views_gw, w->views_gb, w->views_bw, w->views_bb,
+                          w->sigma_w, w->sigma_b};
+    for (const void *p : need)
+        if (!p) return fail(SDFR_EINVAL, "query_ngp_grad: weight pointer is null");
+    for (int l = 0; l < 3; ++l)
+        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
+            !w->pts_bb[l])
+            return fail(SDFR_EINVAL, "query_ngp_grad: FiLM weight pointer is null");
+    uint64_t P;
+    size_t o_film = 0, o_x = 0;
+    const size_t need_ws = grad_ws_layout(a->B, a->M, &P, &o_film, &o_x);
+    if (P >= kGradMaxPoints)
+        return fail(SDFR_EINVAL, "query_ngp_grad: too many points per call (split the points)");
+    if (a->workspace_bytes < need_ws)
+        return fail(SDFR_EINVAL, "query_ngp_grad: workspace too small");
+
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(a->workspace);
+    float *gd = reinterpret_cast<float *>(ws);
+    float *film = reinterpret_cast<float *>(ws + o_film);
+    const uint32_t Mp = (uint32_t)(P / a->B);
+    sdfr_ngp_render_args ra{};            // what the FiLM prep reads of a render call
+    ra.B = a->B;
+    ra.styles = a->styles;
+    ra.prepacked = a->prepacked;
+    int rc;
+    if ((rc = launch_grad_gather(w, a->points, gd, a->B, a->M, Mp, st))) return rc;
+    if ((rc = launch_xprep_ngp(w, &ra, ws + o_x, film, st))) return rc;
+    const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
+    return launch_gfield_ngp(w, xws, film, gd, a->sdf, a->grad, a->B, a->M, Mp, st);
+}
+
 }  // extern "C"

@@ -249,6 +249,59 @@ __device__ __forceinline__ void level_corners(const float *__restrict__ grid,
     }
 }
 
+// The two halves of grid_fwd_kernel's body (encoders.hip) on corner rows already loaded,
+// for kernels that gather a value and its input derivatives from the same rows
+// (field_grad.hip).  grid_fwd_kernel keeps its own text: routing it through these
+// helpers moved the code of all its instantiations (scripts/isa_diff.py), and it is the
+// training path's gather; tests/test_gpu_query_gradient.py holds the two bit-identical.
+//
+// One level's interpolated value from its 2^D corner rows v: corner weights and fma
+// order of gridencoder.cu:160-192 (level_interp).
+template <uint32_t D, uint32_t C>
+__device__ __forceinline__ void level_value(const LevelCoord<D, C> &lc,
+                                            const float (&v)[1u << D][C], float (&res)[C]) {
+#pragma unroll
+    for (uint32_t c = 0; c < C; ++c) res[c] = 0.0f;
+#pragma unroll
+    for (uint32_t idx = 0; idx < (1u << D); ++idx) {
+        float w = 1.0f;
+#pragma unroll
+        for (uint32_t d = 0; d < D; ++d)
+            w = __fmul_rn(w, (idx & (1u << d)) ? lc.pos[d] : __fsub_rn(1.0f, lc.pos[d]));
+#pragma unroll
+        for (uint32_t c = 0; c < C; ++c) res[c] = __fmaf_rn(w, v[idx][c], res[c]);
+    }
+}
+
+// d value / d x_gd of one level from the same corner rows (gridencoder.cu:201-244):
+// differences of the corner pairs along gd, weighted over the other dimensions
+template <uint32_t D, uint32_t C>
+__device__ __forceinline__ void level_dy_dx(const LevelCoord<D, C> &lc, float scale,
+                                            const float (&v)[1u << D][C], uint32_t gd,
+                                            float (&rg)[C]) {
+#pragma unroll
+    for (uint32_t c = 0; c < C; ++c) rg[c] = 0.0f;
+#pragma unroll
+    for (uint32_t idx = 0; idx < (1u << (D - 1)); ++idx) {
+        float w = scale;
+        uint32_t cl = 0;                       // corner with bit gd = 0
+#pragma unroll
+        for (uint32_t nd = 0; nd < D - 1; ++nd) {
+            const uint32_t d = (nd >= gd) ? (nd + 1) : nd;
+            if ((idx & (1u << nd)) == 0) {
+                w = __fmul_rn(w, __fsub_rn(1.0f, lc.pos[d]));
+            } else {
+                w = __fmul_rn(w, lc.pos[d]);
+                cl |= 1u << d;
+            }
+        }
+        const uint32_t cr = cl | (1u << gd);
+#pragma unroll
+        for (uint32_t c = 0; c < C; ++c)
+            rg[c] = __fmaf_rn(__fmul_rn(w, __fsub_rn(v[cr][c], v[cl][c])), lc.pos_d[gd], rg[c]);
+    }
+}
+
 // ----------------------------------------------------------------------------
 // device: ray generation + sampling (sdf_model.py:207-222, 310-351, 363-378)
 // ----------------------------------------------------------------------------

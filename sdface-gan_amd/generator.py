@@ -863,6 +863,17 @@ class Generator(nn.Module):
         lat0 = latent[0][:, 0] if input_is_latent else latent[0]
         return self.renderer.query(points, lat0, viewdirs=viewdirs, return_rgb=return_rgb)
 
+    def query_field_gradient(self, points, styles, truncation=1, truncation_latent=None,
+                             input_is_latent=False, normalize=False, chunk_points=None):
+        """The SDF and its gradient at ``points`` [B,M,3] (network coordinates) for the
+        faces of ``styles``: the mapping network and truncation of ``query_field``, then
+        ``VolumeFeatureRenderer.query_gradient`` -> ``(sdf [B,M], grad [B,M,3])``."""
+        latent = self.styles_and_noise_forward(styles, None, truncation, truncation_latent,
+                                               input_is_latent)
+        lat0 = latent[0][:, 0] if input_is_latent else latent[0]
+        return self.renderer.query_gradient(points, lat0, normalize=normalize,
+                                            chunk_points=chunk_points)
+
     def forward(self, styles, cam_poses, focals, near=0.88, far=1.12, return_latents=False,
                 inject_index=None, truncation=1, truncation_latent=None, input_is_latent=False,
                 noise=None, randomize_noise=True, return_sdf=False, return_xyz=False,

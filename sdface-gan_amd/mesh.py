@@ -15,6 +15,9 @@ Beyond the reference, the field can be queried directly (``VolumeFeatureRenderer
 ``sdfr_query_ngp_forward``): ``sdf_cube`` evaluates the SDF on the cube marching cubes
 reads -- no frustum render, no ``align_volume`` resampling -- and ``color_mesh`` asks the
 field for the colour at every vertex (``Mesh.vertex_colors``, written as ``v x y z r g b``).
+``normal_mesh`` asks it for the SDF's gradient there (``VolumeFeatureRenderer.query_gradient``,
+``sdfr_query_ngp_grad``; ``Mesh.vertex_normals``, written as ``vn x y z``), and
+``eikonal_residual`` gives ``|grad sdf| - 1`` in world units at any points.
 """
 from __future__ import annotations
 
@@ -61,17 +64,21 @@ class Mesh:
     ``trimesh.Trimesh`` the reference returns; trimesh's merge / cleanup
     processing is not applied (vertices are already unique per grid edge)."""
 
-    def __init__(self, vertices, faces, vertex_colors=None):
+    def __init__(self, vertices, faces, vertex_colors=None, vertex_normals=None):
         self.vertices = np.asarray(vertices, np.float32)
         self.faces = np.asarray(faces, np.int64)
         # None, or [V, 3] RGB in [0, 1] (color_mesh)
         self.vertex_colors = (None if vertex_colors is None
                               else np.asarray(vertex_colors, np.float32))
+        # None, or [V, 3] unit normals (normal_mesh)
+        self.vertex_normals = (None if vertex_normals is None
+                               else np.asarray(vertex_normals, np.float32))
 
     def export(self, file_obj=None, file_type="obj"):
         """Wavefront .obj text (``v x y z`` lines -- ``v x y z r g b`` when
-        ``vertex_colors`` is set -- then 1-based ``f a b c``); written to ``file_obj``
-        (an open text file or a path) when given."""
+        ``vertex_colors`` is set -- then 1-based ``f a b c``; with ``vertex_normals`` set,
+        ``vn x y z`` lines follow the ``v`` lines and faces are ``f a//a b//b c//c``);
+        written to ``file_obj`` (an open text file or a path) when given."""
         if file_type != "obj":
             raise ValueError(f"Mesh.export: only 'obj' is supported, not {file_type!r}")
         if self.vertex_colors is None:
@@ -81,7 +88,14 @@ class Mesh:
                 raise ValueError("Mesh.export: vertex_colors must be [V, 3] like vertices")
             lines = ["v %.8f %.8f %.8f %.6f %.6f %.6f" % tuple(v + c) for v, c in
                      zip(self.vertices.tolist(), self.vertex_colors.tolist())]
-        lines += ["f %d %d %d" % tuple(f) for f in (self.faces + 1).tolist()]
+        if self.vertex_normals is None:
+            lines += ["f %d %d %d" % tuple(f) for f in (self.faces + 1).tolist()]
+        else:
+            if self.vertex_normals.shape != self.vertices.shape:
+                raise ValueError("Mesh.export: vertex_normals must be [V, 3] like vertices")
+            lines += ["vn %.6f %.6f %.6f" % tuple(n) for n in self.vertex_normals.tolist()]
+            lines += ["f %d//%d %d//%d %d//%d" % (a, a, b, b, c, c)
+                      for a, b, c in (self.faces + 1).tolist()]
         text = "\n".join(lines) + "\n"
         if file_obj is None:
             return text
@@ -191,6 +205,36 @@ def color_mesh(mesh: Mesh, renderer, styles: torch.Tensor, viewdir=(0.0, 0.0, -1
         _, rgb = renderer.query(pts, styles, viewdirs=vd)
     mesh.vertex_colors = rgb[0].float().cpu().numpy()
     return mesh.vertex_colors
+
+
+def normal_mesh(mesh: Mesh, renderer, styles: torch.Tensor, near: float = 0.88,
+                far: float = 1.12) -> np.ndarray:
+    """The field's unit normal at every vertex of ``mesh`` (world coordinates) for the
+    face ``styles`` [1, 256]: the normalised SDF gradient at ``world_to_network(vertices)``
+    -- the positive uniform scale of ``world_to_network`` does not change directions.  The
+    SDF grows outward, so the normals point out of the surface.  A vertex where the
+    gradient vanishes (outside the hash grid's box) keeps a zero normal.  Sets and returns
+    ``mesh.vertex_normals`` [V, 3]."""
+    if styles.shape[0] != 1:
+        raise ValueError("normal_mesh: one mesh, one face (styles [1, 256])")
+    dev = styles.device
+    pts = world_to_network(torch.as_tensor(mesh.vertices, dtype=torch.float32, device=dev),
+                           near, far).unsqueeze(0)
+    with torch.no_grad():
+        _, n = renderer.query_gradient(pts, styles, normalize=True)
+    mesh.vertex_normals = n[0].float().cpu().numpy()
+    return mesh.vertex_normals
+
+
+def eikonal_residual(renderer, styles: torch.Tensor, points: torch.Tensor, near: float = 0.88,
+                     far: float = 1.12) -> torch.Tensor:
+    """``|grad_world sdf| - 1`` at ``points`` [B, M, 3] (network coordinates): [B, M], zero
+    for a true distance field.  ``query_gradient`` differentiates with respect to the
+    network coordinate p = x_world * 2 / (far - near), so
+    grad_world = grad_network * 2 / (far - near)."""
+    with torch.no_grad():
+        _, g = renderer.query_gradient(points, styles)
+    return (g * (2 / (far - near))).norm(dim=-1) - 1
 
 
 def xyz2mesh(xyz: torch.Tensor):
