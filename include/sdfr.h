@@ -346,6 +346,51 @@ typedef struct sdfr_ngp_grad_args {
 size_t sdfr_query_ngp_grad_workspace_bytes(uint32_t B, uint32_t M);
 int sdfr_query_ngp_grad(const sdfr_ngp_weights *w, const sdfr_ngp_grad_args *a, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Geometry render: the SDF gradient along the camera rays of a render, and normal, depth
+ * and xyz maps composited with the render's weights (added to ABI 15 without a version
+ * step: the two entry points below are additive, nothing existing changes).  Replaces
+ * VolumeFeatureRenderer.forward(return_eikonal=True)'s autograd pass (get_eikonal_term,
+ * sdf_model.py:224-229) at inference.
+ * The samples are those of sdfr_render_ngp_forward for the same cameras, t_vals, t_rand
+ * and sampling flags, in plain [B,H,W,N] order.  They run through sdfr_query_ngp_grad's
+ * gather and forward-mode field kernel as B x (H W N) points, then one compositing kernel:
+ *   sdf      [B,H,W,N]    the render's return_sdf output, bit for bit
+ *   eikonal  [B,H,W,N,3]  d sdf / d world point: the network-coordinate gradient g times
+ *                         2 / (far - near) when z_normalize (fdiv(fmul(g, 2), far - near)),
+ *                         g otherwise; zero for a sample outside the grid's box
+ *   normal   [B,3,H,W]    sum_s w_s eikonal_s (not normalised)
+ *   depth    [B,1,H,W]    sum_s w_s z_s
+ *   xyz      [B,3,H,W]    sum_s w_s (o + d z_s), world points, as the render's xyz
+ *   mask     [B,1,H,W]    w_{N-1}
+ * with the render's weights, front to back in fp32: sigma = sigmoid(-sdf / beta) / beta,
+ * alpha = 1 - exp(-sigma dist), w = alpha T (the last sample's w = 1 - sum of the others
+ * under force_background), T <- T ((1 - alpha) + 1e-10).  Every output may be NULL, at
+ * least one is required.  pix_y may be the renderer's buffer offset by y0 with H = a band
+ * of rows (W stays the image width: the ray directions use W / 2 for both axes).
+ * Workspace: sdfr_query_ngp_grad's for (B, M = H W N) (512 bytes per padded point, M
+ * rounded up to 8 per face, + 8 KiB of FiLM vectors per face + the weight-packing region),
+ * then 36 bytes per padded point: the network coordinates [P][3], (z, dist) [P][2], the
+ * SDF [P] (unused when `sdf` is given) and the network-coordinate gradient [P][3], each
+ * region rounded up to 256 bytes.  SDFR_EINVAL before any launch for null arguments or
+ * required pointers, zero sizes, every output null, a null sigmoid_beta in the weights
+ * (no SDF: no gradient), a workspace below sdfr_render_ngp_geometry_workspace_bytes, or
+ * B x (H W N rounded up to 8) >= 2^25 (the gradient kernels' 32-bit indexing; the size
+ * function returns 0 for such a size); SDFR_EUNSUPPORTED for num_levels != 16.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfr_ngp_geometry_args {
+    uint32_t B, H, W, N;          /* faces, image rows, cols, samples per ray      */
+    const float *cam, *focal, *near_, *far_, *styles, *pix_x, *pix_y, *t_vals;
+    const float *t_rand;          /* as sdfr_ngp_render_args; t_rand may be NULL   */
+    int t_rand_per_sample, offset_sampling, z_normalize, force_background;
+    float *sdf, *eikonal, *normal, *depth, *xyz, *mask;
+    void *workspace; size_t workspace_bytes;
+    const void *prepacked;        /* as sdfr_ngp_query_args.prepacked, or NULL     */
+} sdfr_ngp_geometry_args;
+size_t sdfr_render_ngp_geometry_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t N);
+int sdfr_render_ngp_geometry(const sdfr_ngp_weights *w, const sdfr_ngp_geometry_args *a,
+                             void *stream);
+
 #ifdef SDFR_ABLATION
 /* Profiling hooks, exported only by `make ABLATION=1` builds (lib_abl/libsdfr.so,
  * process-global state; never in the product library):

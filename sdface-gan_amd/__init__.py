@@ -16,7 +16,9 @@ arbitrary points, fused: sdfr_query_ngp_forward), cube_points, sdf_cube, world_t
 color_mesh (meshes from the field itself, vertex colours);
 VolumeFeatureRenderer.query_gradient / Generator.query_field_gradient (the SDF's exact
 gradient, fused: sdfr_query_ngp_grad), normal_mesh, eikonal_residual (vertex normals, the
-eikonal check).
+eikonal check); VolumeFeatureRenderer.render_geometry / Generator.render_geometry -> Geometry
+(the gradient along a render's own rays, normal / depth / xyz maps with the render's weights,
+fused: sdfr_render_ngp_geometry).
   SDFOptions, vol_render_opt                            (sdf_utils.py:447, training_utils.py:144)
 Beyond the reference: GraphedGenerator (HIP-graph replay of the inference forward).
 """
@@ -33,7 +35,7 @@ from .mesh import (Mesh, align_volume, color_mesh, cube_points,  # noqa: F401
                    normal_mesh, sdf_cube, world_to_network, xyz2mesh)
 from .options import AttrDict, SDFOptions, vol_render_opt  # noqa: F401
 from . import training  # noqa: F401  (stage-2 DDP trainer, Discriminator, losses)
-from .renderer import (FCGenerator, FiLMSiren, LinearLayer, NGPSIRENGenerator,  # noqa: F401
-                       SirenGenerator, VolumeFeatureRenderer, get_encoder)
+from .renderer import (FCGenerator, FiLMSiren, Geometry, LinearLayer,  # noqa: F401
+                       NGPSIRENGenerator, SirenGenerator, VolumeFeatureRenderer, get_encoder)
 
 __version__ = "0.1.0"

@@ -38,6 +38,7 @@ EXPORTS = (
     "sdfr_render_ngp_workspace_bytes", "sdfr_render_ngp_forward",
     "sdfr_render_ngp_encode_only", "sdfr_query_ngp_workspace_bytes", "sdfr_query_ngp_forward",
     "sdfr_query_ngp_grad_workspace_bytes", "sdfr_query_ngp_grad",
+    "sdfr_render_ngp_geometry_workspace_bytes", "sdfr_render_ngp_geometry",
     "sdfr_debug_sin_probe",
     "sdfr_debug_sin_rev_probe", "sdfr_camera_extrinsics",
     "sdfr_render_siren_workspace_bytes", "sdfr_render_siren_forward",
@@ -133,6 +134,20 @@ class NgpGradArgs(ctypes.Structure):
     ]
 
 
+class NgpGeometryArgs(ctypes.Structure):
+    """sdfr_ngp_geometry_args (include/sdfr.h)."""
+    _fields_ = [
+        ("B", _u32), ("H", _u32), ("W", _u32), ("N", _u32),
+        ("cam", _vp), ("focal", _vp), ("near_", _vp), ("far_", _vp), ("styles", _vp),
+        ("pix_x", _vp), ("pix_y", _vp), ("t_vals", _vp), ("t_rand", _vp),
+        ("t_rand_per_sample", _int), ("offset_sampling", _int), ("z_normalize", _int),
+        ("force_background", _int),
+        ("sdf", _vp), ("eikonal", _vp), ("normal", _vp), ("depth", _vp), ("xyz", _vp),
+        ("mask", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("prepacked", _vp),
+    ]
+
+
 class StyledEpilogueArgs(ctypes.Structure):
     """sdfr_styled_epilogue_args (include/sdfr.h)."""
     _fields_ = [
@@ -220,6 +235,10 @@ def lib():
     L.sdfr_query_ngp_grad_workspace_bytes.argtypes = [_u32, _u32]
     L.sdfr_query_ngp_grad.argtypes = [ctypes.POINTER(NgpWeights),
                                       ctypes.POINTER(NgpGradArgs), _vp]
+    L.sdfr_render_ngp_geometry_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_render_ngp_geometry_workspace_bytes.argtypes = [_u32, _u32, _u32, _u32]
+    L.sdfr_render_ngp_geometry.argtypes = [ctypes.POINTER(NgpWeights),
+                                           ctypes.POINTER(NgpGeometryArgs), _vp]
     for name in ABLATION_EXPORTS:           # profiling builds only (make ABLATION=1)
         if hasattr(L, name):
             getattr(L, name).argtypes = [_int]

@@ -154,6 +154,15 @@ int launch_grad_gather(const sdfr_ngp_weights *w, const float *points, float *gd
 int launch_gfield_ngp(const sdfr_ngp_weights *w, const char *xws, const float *film,
                       const float *gd, float *sdf, float *grad, uint32_t B, uint32_t M,
                       uint32_t Mp, hipStream_t st);
+// Geometry render (geometry.hip): the cameras' samples in plain [B,H,W,N] order as the
+// gradient gather's points (pnet [S,3], zd [S] = (z, dist), S = B H W N), and the
+// compositing of the gradient call's sdf [S] / gnet [S,3] into per-sample eikonal [S,3]
+// and the normal / depth / xyz / mask maps (each output may be null).
+int launch_geom_points(const GeomArgs &g, float *pnet, float2 *zd, hipStream_t st);
+int launch_geom_composite(const GeomArgs &g, const float2 *zd, const float *sdf,
+                          const float *gnet, const float *sigmoid_beta, int force_background,
+                          float *eikonal, float *normal, float *depth, float *xyz, float *mask,
+                          hipStream_t st);
 // sample-segment split of the f16x3 field kernel for small batches
 constexpr uint32_t kFieldSplitMax = 4;   // sample segments per ray at most
 uint32_t field_nseg(uint32_t B, uint32_t tiles_per_face, uint32_t N, int force_background,

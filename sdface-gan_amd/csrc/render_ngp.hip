@@ -1307,4 +1307,113 @@ int sdfr_query_ngp_grad(const sdfr_ngp_weights *w, const sdfr_ngp_grad_args *a, 
     return launch_gfield_ngp(w, xws, film, gd, a->sdf, a->grad, a->B, a->M, Mp, st);
 }
 
+// ----------------------------------------------------------------------------
+// Geometry render: the gradient call on the cameras' own samples, and normal / depth /
+// xyz / mask maps composited with the render's weights (kernels: geometry.hip)
+// ----------------------------------------------------------------------------
+// the gradient call's workspace for (B, M = H W N) | pnet [P][3] | zd [P] (z, dist) |
+// sdf [P] | gnet [P][3]; P = B Mp padded points, 36 bytes more per padded point.
+// M >= 2^25 alone is too many points (H W N is formed in steps that cannot wrap).
+static size_t geom_ws_layout(uint32_t B, uint32_t H, uint32_t W, uint32_t N, uint32_t *M_out,
+                             size_t *o_film = nullptr, size_t *o_x = nullptr,
+                             size_t *o_pnet = nullptr, size_t *o_zd = nullptr,
+                             size_t *o_sdf = nullptr, size_t *o_gnet = nullptr) {
+    const uint64_t HW = (uint64_t)H * W;
+    if (HW >= kGradMaxPoints || HW * N >= kGradMaxPoints) return 0;
+    const uint32_t M = (uint32_t)(HW * N);
+    if (M_out) *M_out = M;
+    uint64_t P;
+    size_t off = grad_ws_layout(B, M, &P, o_film, o_x);
+    if (P >= kGradMaxPoints) return 0;
+    if (o_pnet) *o_pnet = off;
+    off += align256((size_t)P * 3 * sizeof(float));
+    if (o_zd) *o_zd = off;
+    off += align256((size_t)P * 2 * sizeof(float));
+    if (o_sdf) *o_sdf = off;
+    off += align256((size_t)P * sizeof(float));
+    if (o_gnet) *o_gnet = off;
+    off += align256((size_t)P * 3 * sizeof(float));
+    return off;
+}
+
+size_t sdfr_render_ngp_geometry_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t N) {
+    if (B == 0 || H == 0 || W == 0 || N == 0) return 0;
+    return geom_ws_layout(B, H, W, N, nullptr);
+}
+
+int sdfr_render_ngp_geometry(const sdfr_ngp_weights *w, const sdfr_ngp_geometry_args *a,
+                             void *stream) {
+    if (!w || !a) return fail(SDFR_EINVAL, "render_ngp_geometry: null args");
+    if (w->num_levels != 16)
+        return fail(SDFR_EUNSUPPORTED,
+                    "render_ngp_geometry: fused path needs 16 levels x 2 features");
+    if (a->B == 0 || a->H == 0 || a->W == 0 || a->N == 0)
+        return fail(SDFR_EINVAL, "render_ngp_geometry: empty batch / image / sample count");
+    if (!a->cam || !a->focal || !a->near_ || !a->far_ || !a->styles || !a->pix_x || !a->pix_y ||
+        !a->t_vals || !a->workspace)
+        return fail(SDFR_EINVAL, "render_ngp_geometry: required pointer is null");
+    if (!a->sdf && !a->eikonal && !a->normal && !a->depth && !a->xyz && !a->mask)
+        return fail(SDFR_EINVAL, "render_ngp_geometry: every output is null");
+    const void *need[] = {w->embeddings, w->offsets, w->input_w, w->input_b, w->views_w,
+                          w->views_b, w->views_gw, w->views_gb, w->views_bw, w->views_bb,
+                          w->sigma_w, w->sigma_b};
+    for (const void *p : need)
+        if (!p) return fail(SDFR_EINVAL, "render_ngp_geometry: weight pointer is null");
+    for (int l = 0; l < 3; ++l)
+        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
+            !w->pts_bb[l])
+            return fail(SDFR_EINVAL, "render_ngp_geometry: FiLM weight pointer is null");
+    if (!w->sigmoid_beta)
+        return fail(SDFR_EINVAL, "render_ngp_geometry: sigmoid_beta is required (no SDF, no gradient)");
+    uint32_t M = 0;
+    size_t o_film = 0, o_x = 0, o_pnet = 0, o_zd = 0, o_sdf = 0, o_gnet = 0;
+    const size_t need_ws =
+        geom_ws_layout(a->B, a->H, a->W, a->N, &M, &o_film, &o_x, &o_pnet, &o_zd, &o_sdf, &o_gnet);
+    if (need_ws == 0)
+        return fail(SDFR_EINVAL,
+                    "render_ngp_geometry: too many points per call (split the batch or the rows)");
+    if (a->workspace_bytes < need_ws)
+        return fail(SDFR_EINVAL, "render_ngp_geometry: workspace too small");
+
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(a->workspace);
+    float *gd = reinterpret_cast<float *>(ws);
+    float *film = reinterpret_cast<float *>(ws + o_film);
+    float *pnet = reinterpret_cast<float *>(ws + o_pnet);
+    float2 *zd = reinterpret_cast<float2 *>(ws + o_zd);
+    float *sdf = a->sdf ? a->sdf : reinterpret_cast<float *>(ws + o_sdf);
+    float *gnet = reinterpret_cast<float *>(ws + o_gnet);
+    const uint32_t Mp = (M + kGradPts - 1) / kGradPts * kGradPts;
+    sdfr_ngp_render_args ra{};            // the sampling fields fill_geom_args / the FiLM prep read
+    ra.B = a->B;
+    ra.H = a->H;
+    ra.W = a->W;
+    ra.N = a->N;
+    ra.cam = a->cam;
+    ra.focal = a->focal;
+    ra.near_ = a->near_;
+    ra.far_ = a->far_;
+    ra.styles = a->styles;
+    ra.pix_x = a->pix_x;
+    ra.pix_y = a->pix_y;
+    ra.t_vals = a->t_vals;
+    ra.t_rand = a->t_rand;
+    ra.t_rand_per_sample = a->t_rand_per_sample;
+    ra.offset_sampling = a->offset_sampling;
+    ra.z_normalize = a->z_normalize;
+    ra.prepacked = a->prepacked;
+    GeomArgs g;
+    fill_geom_args(&ra, w->bound, g);
+    const bool composite = a->eikonal || a->normal || a->depth || a->xyz || a->mask;
+    int rc;
+    if ((rc = launch_geom_points(g, pnet, zd, st))) return rc;
+    if ((rc = launch_grad_gather(w, pnet, gd, a->B, M, Mp, st))) return rc;
+    if ((rc = launch_xprep_ngp(w, &ra, ws + o_x, film, st))) return rc;
+    const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
+    if ((rc = launch_gfield_ngp(w, xws, film, gd, sdf, gnet, a->B, M, Mp, st))) return rc;
+    if (!composite) return SDFR_OK;
+    return launch_geom_composite(g, zd, sdf, gnet, w->sigmoid_beta, a->force_background,
+                                 a->eikonal, a->normal, a->depth, a->xyz, a->mask, st);
+}
+
 }  // extern "C"

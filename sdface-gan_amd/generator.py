@@ -874,6 +874,17 @@ class Generator(nn.Module):
         return self.renderer.query_gradient(points, lat0, normalize=normalize,
                                             chunk_points=chunk_points)
 
+    def render_geometry(self, styles, cam_poses, focals, near, far, truncation=1,
+                        truncation_latent=None, input_is_latent=False, **kw):
+        """The geometry of the faces of ``styles`` seen from ``cam_poses``: the mapping
+        network and truncation of ``query_field_gradient``, then
+        ``VolumeFeatureRenderer.render_geometry`` (``kw``: t_rand, want, normalize,
+        chunk_points) -> ``Geometry``.  Not part of the forward graph cache."""
+        latent = self.styles_and_noise_forward(styles, None, truncation, truncation_latent,
+                                               input_is_latent)
+        lat0 = latent[0][:, 0] if input_is_latent else latent[0]
+        return self.renderer.render_geometry(cam_poses, focals, near, far, lat0, **kw)
+
     def forward(self, styles, cam_poses, focals, near=0.88, far=1.12, return_latents=False,
                 inject_index=None, truncation=1, truncation_latent=None, input_is_latent=False,
                 noise=None, randomize_noise=True, return_sdf=False, return_xyz=False,

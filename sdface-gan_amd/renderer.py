@@ -19,6 +19,7 @@ structure on the GPU, with the hash-grid and SH encoders on the HIP kernels.
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -275,6 +276,11 @@ def _opt(opt, key, default=None):
 def _per_face(x, B, device):
     t = torch.as_tensor(x, dtype=torch.float32, device=device).reshape(-1)
     return (t.expand(B) if t.numel() == 1 else t).contiguous()
+
+
+# What VolumeFeatureRenderer.render_geometry returns: NCHW maps and the per-sample SDF and
+# eikonal term in forward's layout; fields that were not asked for are None.
+Geometry = namedtuple("Geometry", ("normal", "depth", "xyz", "mask", "sdf", "eikonal"))
 
 
 class VolumeFeatureRenderer(nn.Module):
@@ -901,6 +907,209 @@ class VolumeFeatureRenderer(nn.Module):
             gd = ws[:B * Mp * 512].view(torch.float32).view(B, Mp, 4, 32)[:, :M]
             return gd[:, :, 0].clone(), gd[:, :, 1:].clone()
         return sdf, grad
+
+    # ---------------------------------------------------------------- geometry render
+    GEOMETRY_FIELDS = ("normal", "depth", "xyz", "mask", "sdf", "eikonal")
+
+    def render_geometry(self, cam_poses, focal, near, far, styles, t_rand=None,
+                        want=("normal", "depth", "xyz", "mask"), normalize=False,
+                        chunk_points=None):
+        """The geometry of a render: ``Geometry(normal, depth, xyz, mask, sdf, eikonal)``
+        for the cameras of ``forward``; fields not named in ``want`` are ``None``.
+
+        ``sdf`` [B,H,W,N,1] and ``eikonal`` [B,H,W,N,3] are the per-sample SDF and its
+        gradient with respect to the world point, as ``forward(return_eikonal=True)``
+        returns them (sdf_model.py:224-229).  ``normal`` [B,3,H,W] (sum of w eikonal, not
+        normalised unless ``normalize``: then divided by ``max(|normal|, 1e-20)``),
+        ``depth`` [B,1,H,W] (sum of w z), ``xyz`` [B,3,H,W] and ``mask`` [B,1,H,W] are
+        composited with exactly the render's weights.  The sampling flags (``perturb``,
+        ``offset_sampling``, ``z_normalize``, ``force_background``, ``N_samples``,
+        ``out_im_res``) are the renderer's; ``t_rand`` is drawn as in ``forward`` when
+        ``perturb > 0`` and none is given.
+
+        Under the rule of ``query_gradient``'s fused path this runs
+        ``sdfr_render_ngp_geometry`` (the sample points, the gradient call's gather and
+        forward-mode field kernel, a compositing kernel; ``sdf`` is the fused render's
+        ``return_sdf`` output bit for bit), in calls of at most ``chunk_points`` points
+        (default ``GRADIENT_CHUNK_POINTS``) over faces and bands of whole image rows; a
+        single row above the chunk is one call.  Chunking does not change a bit of any
+        output.  Otherwise (SIREN, FC, CPU tensors, the fp32 field, grad mode with
+        something that requires grad) the same definitions are computed op by op, the
+        gradient by autograd with grad enabled locally on detached inputs.  Either way the
+        result carries no autograd graph.
+        """
+        if not self.with_sdf:
+            raise ValueError("render_geometry: the renderer has no SDF (no_sdf)")
+        want = tuple(want)
+        unknown = [k for k in want if k not in self.GEOMETRY_FIELDS]
+        if unknown or not want:
+            raise ValueError(f"render_geometry: want must name some of "
+                             f"{self.GEOMETRY_FIELDS}, got {want}")
+        if self._query_fused_ok(cam_poses, styles):
+            out = self._fused_geometry(cam_poses, focal, near, far, styles, t_rand, want,
+                                       chunk_points)
+        else:
+            out = self._module_geometry(cam_poses, focal, near, far, styles, t_rand, want)
+        if normalize and out.get("normal") is not None:
+            n = out["normal"].norm(dim=1, keepdim=True)
+            out["normal"] = out["normal"] / n.clamp_min(1e-20)
+        return Geometry(**{k: out.get(k) for k in self.GEOMETRY_FIELDS})
+
+    def _fused_geometry(self, cam_poses, focal, near, far, styles, t_rand, want, chunk_points):
+        """``sdfr_render_ngp_geometry`` in calls of whole faces or bands of whole rows."""
+        self._fused_check_params()
+        dev = cam_poses.device
+        B = cam_poses.shape[0]
+        H = W = self.out_im_res
+        N = self.N_samples
+        cam = cam_poses.detach().float().contiguous()
+        focal = _per_face(focal, B, dev)
+        near = _per_face(near, B, dev)
+        far = _per_face(far, B, dev)
+        styles = styles.detach().float().contiguous()
+        per_sample = 0
+        if self.perturb > 0:
+            shape = (B, H, W) if self.offset_sampling else (B, H, W, N)
+            if t_rand is None:
+                t_rand = self._draw_t_rand(shape, dev)
+            t_rand = t_rand.to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
+            per_sample = 0 if self.offset_sampling else 1
+        else:
+            t_rand = None
+        pix_x = self.i[0, 0, :].contiguous()
+        pix_y = self.j[0, :, 0].contiguous()
+        t_vals = self.t_vals.reshape(-1).contiguous()
+        shapes = {"sdf": (B, H, W, N), "eikonal": (B, H, W, N, 3), "normal": (B, 3, H, W),
+                  "depth": (B, 1, H, W), "xyz": (B, 3, H, W), "mask": (B, 1, H, W)}
+        out = {k: torch.empty(shapes[k], device=dev) for k in want}
+        if chunk_points is None:
+            chunk_points = self.GRADIENT_CHUNK_POINTS
+        chunk_points = max(1, int(chunk_points))
+        per_row, per_face = W * N, H * W * N
+        if per_face <= chunk_points:
+            # whole faces; the library takes fewer than 2^25 padded points per call
+            padded = (per_face + 7) // 8 * 8
+            faces, rows = max(1, min(chunk_points // per_face, ((1 << 25) - 1) // padded)), H
+        else:
+            faces, rows = 1, max(1, chunk_points // per_row)
+        L = _lib.lib()
+        prepacked = self._prepacked(0, cam)
+        w = self._weight_struct(0)
+        ws = None
+        for b0 in range(0, B, faces):
+            b1 = min(B, b0 + faces)
+            for y0 in range(0, H, rows):
+                y1 = min(H, y0 + rows)
+                # per-sample outputs of a band are contiguous in the result; a band of a
+                # map is not: it goes through a tensor of its own
+                dst, tmp = {}, {}
+                for k, t in out.items():
+                    v = t[b0:b1, y0:y1] if k in ("sdf", "eikonal") else t[b0:b1, :, y0:y1]
+                    dst[k] = v if v.is_contiguous() else torch.empty(v.shape, device=dev)
+                    if dst[k] is not v:
+                        tmp[k] = v
+                c_rand = None
+                if t_rand is not None:
+                    c_rand = t_rand[b0:b1, y0:y1].contiguous()
+                need = L.sdfr_render_ngp_geometry_workspace_bytes(b1 - b0, y1 - y0, W, N)
+                if ws is None or ws.numel() < need:
+                    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                c_y = pix_y[y0:y1]
+                a = _lib.NgpGeometryArgs(
+                    B=b1 - b0, H=y1 - y0, W=W, N=N, cam=_lib.ptr(cam[b0:b1]),
+                    focal=_lib.ptr(focal[b0:b1]), near_=_lib.ptr(near[b0:b1]),
+                    far_=_lib.ptr(far[b0:b1]), styles=_lib.ptr(styles[b0:b1]),
+                    pix_x=_lib.ptr(pix_x), pix_y=_lib.ptr(c_y), t_vals=_lib.ptr(t_vals),
+                    t_rand=_lib.ptr(c_rand), t_rand_per_sample=per_sample,
+                    offset_sampling=int(self.offset_sampling), z_normalize=int(self.z_normalize),
+                    force_background=int(bool(self.force_background)),
+                    sdf=_lib.ptr(dst.get("sdf")), eikonal=_lib.ptr(dst.get("eikonal")),
+                    normal=_lib.ptr(dst.get("normal")), depth=_lib.ptr(dst.get("depth")),
+                    xyz=_lib.ptr(dst.get("xyz")), mask=_lib.ptr(dst.get("mask")),
+                    workspace=_lib.ptr(ws), workspace_bytes=ws.numel(),
+                    prepacked=_lib.ptr(prepacked))
+                _lib.check(L.sdfr_render_ngp_geometry(ctypes.byref(w), ctypes.byref(a),
+                                                      _lib.stream_of(cam)),
+                           "sdfr_render_ngp_geometry")
+                for k, v in tmp.items():
+                    v.copy_(dst[k])
+        if "sdf" in out:
+            out["sdf"] = out["sdf"].unsqueeze(-1)
+        return out
+
+    def _geometry_weights(self, sdf, z_vals, rays_d):
+        """The compositing weights [B,H,W,N,1] of ``volume_integration`` from a per-sample
+        SDF [B,H,W,N,1] (the geometry render's module path; no autograd graph)."""
+        with torch.no_grad():
+            dists = z_vals[..., 1:] - z_vals[..., :-1]
+            rays_d_norm = torch.norm(rays_d.unsqueeze(self.samples_dim), dim=self.channel_dim)
+            dists = torch.cat([dists, self.inf.expand(rays_d_norm.shape)], self.channel_dim)
+            dists = dists * rays_d_norm
+            sigma = self.sdf_activation(-sdf)
+            sigma = 1 - torch.exp(-sigma * dists.unsqueeze(self.channel_dim))
+            first = torch.ones_like(torch.index_select(sigma, self.samples_dim, self.zero_idx))
+            visibility = torch.cumprod(torch.cat([first, 1. - sigma + 1e-10], self.samples_dim),
+                                       self.samples_dim)[..., :-1, :]
+            weights = sigma * visibility
+            if self.force_background:
+                weights[..., -1, :] = 1 - weights[..., :-1, :].sum(self.samples_dim)
+        return weights
+
+    def _module_geometry(self, cam_poses, focal, near, far, styles, t_rand, want):
+        """``render_geometry`` op by op: the rays and samples of ``render`` /
+        ``render_rays``, the gradient by autograd on detached inputs."""
+        cam_poses, focal, near, far = (t.detach() for t in (cam_poses, focal, near, far))
+        styles = styles.detach() if styles is not None else None
+        with torch.no_grad():
+            rays_o, rays_d, viewdirs = self.get_rays(focal, cam_poses)
+            viewdirs = viewdirs / torch.norm(viewdirs, dim=-1, keepdim=True)
+            near = near.unsqueeze(-1) * torch.ones_like(rays_d[..., :1])
+            far = far.unsqueeze(-1) * torch.ones_like(rays_d[..., :1])
+            rays = torch.cat([rays_o, rays_d, near, far, viewdirs], -1).float()
+            rays_o, rays_d, bounds, viewdirs = torch.split(rays, [3, 3, 2, 3], dim=-1)
+            near, far = torch.split(bounds, [1, 1], dim=-1)
+            batch, h, w, _ = rays.shape
+            z_vals = near * (1. - self.t_vals) + far * self.t_vals
+            if self.perturb > 0.:
+                if self.offset_sampling:
+                    upper = torch.cat([z_vals[..., 1:], far], -1)
+                    lower = z_vals
+                    if t_rand is None:
+                        t_rand = self._draw_t_rand((batch, h, w), z_vals.device)
+                    t_rand = t_rand.to(z_vals.device).reshape(batch, h, w, 1)
+                else:
+                    mids = .5 * (z_vals[..., 1:] + z_vals[..., :-1])
+                    upper = torch.cat([mids, z_vals[..., -1:]], -1)
+                    lower = torch.cat([z_vals[..., :1], mids], -1)
+                    if t_rand is None:
+                        t_rand = self._draw_t_rand(z_vals.shape, z_vals.device)
+                    t_rand = t_rand.to(z_vals.device).reshape(z_vals.shape)
+                z_vals = lower + (upper - lower) * t_rand
+            pts = rays_o.unsqueeze(3) + rays_d.unsqueeze(3) * z_vals.unsqueeze(-1)
+        with torch.enable_grad():
+            pts = pts.requires_grad_(True)
+            normalized_pts = pts * 2 / ((far - near).unsqueeze(3)) if self.z_normalize else pts
+            raw = self.run_network(normalized_pts, viewdirs, styles=styles)
+            sdf = raw[..., 3:4]
+            eikonal, = autograd.grad(outputs=sdf, inputs=pts, grad_outputs=torch.ones_like(sdf))
+        sdf, pts = sdf.detach(), pts.detach()
+        out = {}
+        if "sdf" in want:
+            out["sdf"] = sdf
+        if "eikonal" in want:
+            out["eikonal"] = eikonal
+        if any(k in want for k in ("normal", "depth", "xyz", "mask")):
+            weights = self._geometry_weights(sdf, z_vals, rays_d)
+            with torch.no_grad():
+                maps = {"normal": lambda: torch.sum(weights * eikonal, self.samples_dim),
+                        "depth": lambda: torch.sum(weights * z_vals.unsqueeze(-1),
+                                                   self.samples_dim),
+                        "xyz": lambda: torch.sum(weights * pts, self.samples_dim),
+                        "mask": lambda: weights[..., -1, :]}
+                for k, fn in maps.items():
+                    if k in want:
+                        out[k] = fn().permute(0, 3, 1, 2).contiguous()
+        return out
 
     # ---------------------------------------------------------------- API
     def forward(self, cam_poses, focal, near, far, styles=None, return_eikonal=False,
