@@ -2142,14 +2142,14 @@ static int launch_xpack(const NetPtrs &P, uint32_t B, const float *styles, char 
 }
 
 // Per call: FiLM vectors of the batch, and the weight packing unless the caller
-// passed weights packed beforehand (a->prepacked, f16x3 only).
+// passed weights packed beforehand (prepacked, f16x3 only).
 template <class Net>
-static int launch_xprep(const NetPtrs &P, const sdfr_ngp_render_args *a, char *xws, float *film,
-                        hipStream_t st) {
-    if (a->prepacked)
-        return launch_xpack<Net>(P, a->B, a->styles, const_cast<char *>(
-                                     reinterpret_cast<const char *>(a->prepacked)), film, false, st);
-    return launch_xpack<Net>(P, a->B, a->styles, xws, film, true, st);
+static int launch_xprep(const NetPtrs &P, uint32_t B, const float *styles, const void *prepacked,
+                        char *xws, float *film, hipStream_t st) {
+    if (prepacked)
+        return launch_xpack<Net>(P, B, styles, const_cast<char *>(
+                                     reinterpret_cast<const char *>(prepacked)), film, false, st);
+    return launch_xpack<Net>(P, B, styles, xws, film, true, st);
 }
 
 template <class Net>
@@ -2235,9 +2235,9 @@ static NetPtrs ngp_ptrs(const sdfr_ngp_weights *w) {
     return P;
 }
 
-int launch_xprep_ngp(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, char *xws,
-                     float *film, hipStream_t st) {
-    return launch_xprep<NgpNet>(ngp_ptrs(w), a, xws, film, st);
+int launch_xprep_ngp(const sdfr_ngp_weights *w, uint32_t B, const float *styles,
+                     const void *prepacked, char *xws, float *film, hipStream_t st) {
+    return launch_xprep<NgpNet>(ngp_ptrs(w), B, styles, prepacked, xws, film, st);
 }
 
 int launch_xfield_ngp(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a,
@@ -2396,10 +2396,11 @@ int sdfr_render_fc_forward(const sdfr_fc_weights *w, const sdfr_ngp_render_args 
     float *film = reinterpret_cast<float *>(ws);
     const NetPtrs P = fc_ptrs(w);
     GeomArgs g;
-    fill_geom_args(a, 1.0f, g);
+    fill_geom_args(a, a->static_viewdirs, 1.0f, g);
     record_event(a->stage_events[0], st);
     wait_event(a->styles_event, st);
-    if ((rc = launch_xprep<FcNet>(P, a, ws + o_x, film, st))) return rc;
+    if ((rc = launch_xprep<FcNet>(P, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
+        return rc;
     record_event(a->stage_events[1], st);
     record_event(a->stage_events[2], st);
     record_event(a->field_event, st);
@@ -2437,10 +2438,11 @@ int sdfr_render_siren_forward(const sdfr_siren_weights *w, const sdfr_ngp_render
     float *film = reinterpret_cast<float *>(ws);
     const NetPtrs P = siren_ptrs(w);
     GeomArgs g;
-    fill_geom_args(a, 1.0f, g);
+    fill_geom_args(a, a->static_viewdirs, 1.0f, g);
     record_event(a->stage_events[0], st);
     wait_event(a->styles_event, st);
-    if ((rc = launch_xprep<SirenNet>(P, a, ws + o_x, film, st))) return rc;
+    if ((rc = launch_xprep<SirenNet>(P, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
+        return rc;
     record_event(a->stage_events[1], st);
     record_event(a->stage_events[2], st);
     record_event(a->field_event, st);

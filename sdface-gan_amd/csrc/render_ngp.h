@@ -131,8 +131,10 @@ __device__ __forceinline__ float group_sum(float v) {
 // scales and scaled biases.
 size_t f16x3_ws_bytes(int net);
 int field_variant();   // profiling ablation selected by sdfr_debug_set_field_variant
-int launch_xprep_ngp(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, char *xws,
-                     float *film, hipStream_t st);
+// FiLM vectors of the B faces' styles, and the weight packing into xws unless the caller
+// passed weights packed beforehand (prepacked non-null)
+int launch_xprep_ngp(const sdfr_ngp_weights *w, uint32_t B, const float *styles,
+                     const void *prepacked, char *xws, float *film, hipStream_t st);
 int launch_xfield_ngp(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a,
                       const GeomArgs &g, const float *enc, char *xws, const float *film,
                       hipStream_t st, float *part, const float2 *zd);
@@ -168,7 +170,33 @@ constexpr uint32_t kFieldSplitMax = 4;   // sample segments per ray at most
 uint32_t field_nseg(uint32_t B, uint32_t tiles_per_face, uint32_t N, int force_background,
                     uint32_t max_seg);
 size_t field_part_bytes(uint32_t B, uint32_t tiles_per_face, uint32_t N);
-void fill_geom_args(const sdfr_ngp_render_args *a, float bound, GeomArgs &g);
+// the camera / sampling fields of a render or geometry call (sdfr_ngp_render_args,
+// sdfr_ngp_geometry_args: the shared fields have the same names)
+template <class Args>
+void fill_geom_args(const Args *a, int static_viewdirs, float bound, GeomArgs &g) {
+    g.B = a->B;
+    g.H = a->H;
+    g.W = a->W;
+    g.N = a->N;
+    g.tiles_per_face = (a->H * a->W + kTileRays - 1) / kTileRays;
+    g.total_tiles = a->B * g.tiles_per_face;
+    g.S_total = g.total_tiles * a->N * kTileRays;
+    g.half_res = (float)a->W * 0.5f;   // get_rays uses out_im_res * .5 for both axes
+    g.cam = a->cam;
+    g.focal = a->focal;
+    g.near_ = a->near_;
+    g.far_ = a->far_;
+    g.pix_x = a->pix_x;
+    g.pix_y = a->pix_y;
+    g.sc.t_vals = a->t_vals;
+    g.sc.t_rand = a->t_rand;
+    g.sc.t_rand_per_sample = a->t_rand_per_sample;
+    g.sc.offset_sampling = a->offset_sampling;
+    g.sc.N = a->N;
+    g.static_viewdirs = static_viewdirs;
+    g.z_normalize = a->z_normalize;
+    g.bound = bound;
+}
 void record_event(void *ev, hipStream_t st);
 // stream waits on a caller's hipEvent_t (NULL: nothing)
 void wait_event(void *ev, hipStream_t st);

@@ -825,10 +825,28 @@ static size_t ws_layout(uint32_t B, uint32_t H, uint32_t W, uint32_t N, uint32_t
     return off;
 }
 
+// The ngp network's shape and weight pointers, for every entry point that takes
+// sdfr_ngp_weights (`who` prefixes the message; need_rgb: the colour head is read too).
+static int check_ngp_weights(const sdfr_ngp_weights *w, const char *who, bool need_rgb) {
+    const std::string p = std::string(who) + ": ";
+    if (w->num_levels != 16)
+        return fail(SDFR_EUNSUPPORTED, p + "fused path needs 16 levels x 2 features");
+    const void *need[] = {w->embeddings, w->offsets, w->input_w, w->input_b, w->views_w,
+                          w->views_b, w->views_gw, w->views_gb, w->views_bw, w->views_bb,
+                          w->sigma_w, w->sigma_b};
+    for (const void *q : need)
+        if (!q) return fail(SDFR_EINVAL, p + "weight pointer is null");
+    if (need_rgb && (!w->rgb_w || !w->rgb_b))
+        return fail(SDFR_EINVAL, p + "weight pointer is null");
+    for (int l = 0; l < 3; ++l)
+        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
+            !w->pts_bb[l])
+            return fail(SDFR_EINVAL, p + "FiLM weight pointer is null");
+    return SDFR_OK;
+}
+
 static int validate(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a) {
     if (!w || !a) return fail(SDFR_EINVAL, "render_ngp: null args");
-    if (w->num_levels != 16)
-        return fail(SDFR_EUNSUPPORTED, "render_ngp: fused path needs 16 levels x 2 features");
     if (a->B == 0 || a->H == 0 || a->W == 0 || a->N == 0)
         return fail(SDFR_EINVAL, "render_ngp: empty batch / image / sample count");
     if (a->field_precision != SDFR_FIELD_F16X3 && a->field_precision != SDFR_FIELD_FP32)
@@ -838,11 +856,7 @@ static int validate(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a) {
     if (!a->cam || !a->focal || !a->near_ || !a->far_ || !a->styles || !a->pix_x ||
         !a->pix_y || !a->t_vals || !a->rgb || !a->workspace)
         return fail(SDFR_EINVAL, "render_ngp: required pointer is null");
-    const void *need[] = {w->embeddings, w->offsets, w->input_w, w->input_b, w->views_w,
-                          w->views_b, w->views_gw, w->views_gb, w->views_bw, w->views_bb,
-                          w->sigma_w, w->sigma_b, w->rgb_w, w->rgb_b};
-    for (const void *p : need)
-        if (!p) return fail(SDFR_EINVAL, "render_ngp: weight pointer is null");
+    if (int rc = check_ngp_weights(w, "render_ngp", true)) return rc;
     if (a->with_sdf && !w->sigmoid_beta)
         return fail(SDFR_EINVAL, "render_ngp: sigmoid_beta is required when with_sdf");
     if (a->features_split) {
@@ -851,10 +865,6 @@ static int validate(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a) {
         if (a->features || !a->features_mod)
             return fail(SDFR_EINVAL, "render_ngp: features_split takes features_mod and no features");
     }
-    for (int l = 0; l < 3; ++l)
-        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
-            !w->pts_bb[l])
-            return fail(SDFR_EINVAL, "render_ngp: FiLM weight pointer is null");
     size_t op, of;
     if (a->workspace_bytes < ws_layout(a->B, a->H, a->W, a->N, 16, &op, &of))
         return fail(SDFR_EINVAL, "render_ngp: workspace too small");
@@ -865,32 +875,7 @@ static int validate(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a) {
 }
 
 static void fill_geom(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, GeomArgs &g) {
-    fill_geom_args(a, w->bound, g);
-}
-
-void fill_geom_args(const sdfr_ngp_render_args *a, float bound, GeomArgs &g) {
-    g.B = a->B;
-    g.H = a->H;
-    g.W = a->W;
-    g.N = a->N;
-    g.tiles_per_face = (a->H * a->W + kTileRays - 1) / kTileRays;
-    g.total_tiles = a->B * g.tiles_per_face;
-    g.S_total = g.total_tiles * a->N * kTileRays;
-    g.half_res = (float)a->W * 0.5f;   // get_rays uses out_im_res * .5 for both axes
-    g.cam = a->cam;
-    g.focal = a->focal;
-    g.near_ = a->near_;
-    g.far_ = a->far_;
-    g.pix_x = a->pix_x;
-    g.pix_y = a->pix_y;
-    g.sc.t_vals = a->t_vals;
-    g.sc.t_rand = a->t_rand;
-    g.sc.t_rand_per_sample = a->t_rand_per_sample;
-    g.sc.offset_sampling = a->offset_sampling;
-    g.sc.N = a->N;
-    g.static_viewdirs = a->static_viewdirs;
-    g.z_normalize = a->z_normalize;
-    g.bound = bound;
+    fill_geom_args(a, a->static_viewdirs, w->bound, g);
 }
 
 void record_event(void *ev, hipStream_t st) {
@@ -984,8 +969,8 @@ static int launch_geom(const GeomArgs &g, float2 *zd, f4 *gu, hipStream_t st) {
     return check_launch("render_ngp: sample geometry");
 }
 
-static int launch_encode(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a,
-                         const GeomArgs &g, float *enc, const f4 *gu, hipStream_t st) {
+static int launch_encode(const sdfr_ngp_weights *w, const GeomArgs &g, float *enc, const f4 *gu,
+                         hipStream_t st) {
     EncodeArgs e;
     e.g = g;
     e.emb = w->embeddings;
@@ -1089,7 +1074,7 @@ int sdfr_render_ngp_encode_only(const sdfr_ngp_weights *w, const sdfr_ngp_render
     f4 *gu = reinterpret_cast<f4 *>(ws + o_gu);
     hipStream_t st = (hipStream_t)stream;
     if ((rc = launch_geom(g, nullptr, gu, st))) return rc;
-    return launch_encode(w, a, g, reinterpret_cast<float *>(ws), gu, st);
+    return launch_encode(w, g, reinterpret_cast<float *>(ws), gu, st);
 }
 
 int sdfr_render_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a,
@@ -1114,10 +1099,11 @@ int sdfr_render_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_render_arg
         float2 *zd = reinterpret_cast<float2 *>(ws + o_zd);
         if ((rc = launch_geom(g, zd, gu, st))) return rc;
         record_event(a->stage_events[1], st);                  // the encode stage is the gather alone
-        if ((rc = launch_encode(w, a, g, enc, gu, st))) return rc;
+        if ((rc = launch_encode(w, g, enc, gu, st))) return rc;
         record_event(a->stage_events[2], st);
         wait_event(a->styles_event, st);
-        if ((rc = launch_xprep_ngp(w, a, ws + o_x, film, st))) return rc;
+        if ((rc = launch_xprep_ngp(w, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
+            return rc;
         record_event(a->field_event, st);
         float *part = reinterpret_cast<float *>(ws + o_part);
         if ((rc = launch_xfield_ngp(w, a, g, enc, ws + o_x, film, st, part, zd))) return rc;
@@ -1128,7 +1114,7 @@ int sdfr_render_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_render_arg
     if ((rc = launch_prep(w, a, packed, film, st))) return rc;
     if ((rc = launch_geom(g, nullptr, gu, st))) return rc;
     record_event(a->stage_events[1], st);
-    if ((rc = launch_encode(w, a, g, enc, gu, st))) return rc;
+    if ((rc = launch_encode(w, g, enc, gu, st))) return rc;
     record_event(a->stage_events[2], st);
     record_event(a->field_event, st);
 
@@ -1189,21 +1175,12 @@ size_t sdfr_query_ngp_workspace_bytes(uint32_t B, uint32_t R, uint32_t N) {
 int sdfr_query_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_query_args *a,
                            void *stream) {
     if (!w || !a) return fail(SDFR_EINVAL, "query_ngp: null args");
-    if (w->num_levels != 16)
-        return fail(SDFR_EUNSUPPORTED, "query_ngp: fused path needs 16 levels x 2 features");
     if (a->B == 0 || a->R == 0 || a->N == 0)
         return fail(SDFR_EINVAL, "query_ngp: empty batch / group / point count");
     if (!a->points || !a->dirs || !a->styles || !a->sdf || !a->workspace)
         return fail(SDFR_EINVAL, "query_ngp: required pointer is null");
-    const void *need[] = {w->embeddings, w->offsets, w->input_w, w->input_b, w->views_w,
-                          w->views_b, w->views_gw, w->views_gb, w->views_bw, w->views_bb,
-                          w->sigma_w, w->sigma_b, w->rgb_w, w->rgb_b};
-    for (const void *p : need)
-        if (!p) return fail(SDFR_EINVAL, "query_ngp: weight pointer is null");
-    for (int l = 0; l < 3; ++l)
-        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
-            !w->pts_bb[l])
-            return fail(SDFR_EINVAL, "query_ngp: FiLM weight pointer is null");
+    int rc = check_ngp_weights(w, "query_ngp", true);
+    if (rc) return rc;
     // the limit of the render (validate: 16 S < 2^32) and the field kernel's 32-bit byte
     // offsets into enc (128 S < 2^32); group and tile counts fit 32 bits below it
     uint64_t S;
@@ -1228,14 +1205,10 @@ int sdfr_query_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_query_args 
     g.S_total = (uint32_t)S;
     g.cam = a->dirs;
     g.bound = w->bound;
-    sdfr_ngp_render_args ra{};            // what the FiLM prep reads of a render call
-    ra.B = a->B;
-    ra.styles = a->styles;
-    ra.prepacked = a->prepacked;
-    int rc;
     if ((rc = launch_query_geom(a->points, gu, g, st))) return rc;
-    if ((rc = launch_encode(w, &ra, g, enc, gu, st))) return rc;
-    if ((rc = launch_xprep_ngp(w, &ra, ws + o_x, film, st))) return rc;
+    if ((rc = launch_encode(w, g, enc, gu, st))) return rc;
+    if ((rc = launch_xprep_ngp(w, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
+        return rc;
     const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
     return launch_qfield_ngp(w, g, enc, xws, film, a->sdf, a->rgb, st);
 }
@@ -1269,20 +1242,11 @@ size_t sdfr_query_ngp_grad_workspace_bytes(uint32_t B, uint32_t M) {
 
 int sdfr_query_ngp_grad(const sdfr_ngp_weights *w, const sdfr_ngp_grad_args *a, void *stream) {
     if (!w || !a) return fail(SDFR_EINVAL, "query_ngp_grad: null args");
-    if (w->num_levels != 16)
-        return fail(SDFR_EUNSUPPORTED, "query_ngp_grad: fused path needs 16 levels x 2 features");
     if (a->B == 0 || a->M == 0) return fail(SDFR_EINVAL, "query_ngp_grad: empty batch / point count");
     if (!a->points || !a->styles || !a->grad || !a->workspace)
         return fail(SDFR_EINVAL, "query_ngp_grad: required pointer is null");
-    const void *need[] = {w->embeddings, w->offsets, w->input_w, w->input_b, w->views_w,
-                          w->views_b, w->views_gw, w->views_gb, w->views_bw, w->views_bb,
-                          w->sigma_w, w->sigma_b};
-    for (const void *p : need)
-        if (!p) return fail(SDFR_EINVAL, "query_ngp_grad: weight pointer is null");
-    for (int l = 0; l < 3; ++l)
-        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
-            !w->pts_bb[l])
-            return fail(SDFR_EINVAL, "query_ngp_grad: FiLM weight pointer is null");
+    int rc = check_ngp_weights(w, "query_ngp_grad", false);
+    if (rc) return rc;
     uint64_t P;
     size_t o_film = 0, o_x = 0;
     const size_t need_ws = grad_ws_layout(a->B, a->M, &P, &o_film, &o_x);
@@ -1296,13 +1260,9 @@ int sdfr_query_ngp_grad(const sdfr_ngp_weights *w, const sdfr_ngp_grad_args *a, 
     float *gd = reinterpret_cast<float *>(ws);
     float *film = reinterpret_cast<float *>(ws + o_film);
     const uint32_t Mp = (uint32_t)(P / a->B);
-    sdfr_ngp_render_args ra{};            // what the FiLM prep reads of a render call
-    ra.B = a->B;
-    ra.styles = a->styles;
-    ra.prepacked = a->prepacked;
-    int rc;
     if ((rc = launch_grad_gather(w, a->points, gd, a->B, a->M, Mp, st))) return rc;
-    if ((rc = launch_xprep_ngp(w, &ra, ws + o_x, film, st))) return rc;
+    if ((rc = launch_xprep_ngp(w, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
+        return rc;
     const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
     return launch_gfield_ngp(w, xws, film, gd, a->sdf, a->grad, a->B, a->M, Mp, st);
 }
@@ -1344,9 +1304,6 @@ size_t sdfr_render_ngp_geometry_workspace_bytes(uint32_t B, uint32_t H, uint32_t
 int sdfr_render_ngp_geometry(const sdfr_ngp_weights *w, const sdfr_ngp_geometry_args *a,
                              void *stream) {
     if (!w || !a) return fail(SDFR_EINVAL, "render_ngp_geometry: null args");
-    if (w->num_levels != 16)
-        return fail(SDFR_EUNSUPPORTED,
-                    "render_ngp_geometry: fused path needs 16 levels x 2 features");
     if (a->B == 0 || a->H == 0 || a->W == 0 || a->N == 0)
         return fail(SDFR_EINVAL, "render_ngp_geometry: empty batch / image / sample count");
     if (!a->cam || !a->focal || !a->near_ || !a->far_ || !a->styles || !a->pix_x || !a->pix_y ||
@@ -1354,15 +1311,8 @@ int sdfr_render_ngp_geometry(const sdfr_ngp_weights *w, const sdfr_ngp_geometry_
         return fail(SDFR_EINVAL, "render_ngp_geometry: required pointer is null");
     if (!a->sdf && !a->eikonal && !a->normal && !a->depth && !a->xyz && !a->mask)
         return fail(SDFR_EINVAL, "render_ngp_geometry: every output is null");
-    const void *need[] = {w->embeddings, w->offsets, w->input_w, w->input_b, w->views_w,
-                          w->views_b, w->views_gw, w->views_gb, w->views_bw, w->views_bb,
-                          w->sigma_w, w->sigma_b};
-    for (const void *p : need)
-        if (!p) return fail(SDFR_EINVAL, "render_ngp_geometry: weight pointer is null");
-    for (int l = 0; l < 3; ++l)
-        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
-            !w->pts_bb[l])
-            return fail(SDFR_EINVAL, "render_ngp_geometry: FiLM weight pointer is null");
+    int rc = check_ngp_weights(w, "render_ngp_geometry", false);
+    if (rc) return rc;
     if (!w->sigmoid_beta)
         return fail(SDFR_EINVAL, "render_ngp_geometry: sigmoid_beta is required (no SDF, no gradient)");
     uint32_t M = 0;
@@ -1384,31 +1334,13 @@ int sdfr_render_ngp_geometry(const sdfr_ngp_weights *w, const sdfr_ngp_geometry_
     float *sdf = a->sdf ? a->sdf : reinterpret_cast<float *>(ws + o_sdf);
     float *gnet = reinterpret_cast<float *>(ws + o_gnet);
     const uint32_t Mp = (M + kGradPts - 1) / kGradPts * kGradPts;
-    sdfr_ngp_render_args ra{};            // the sampling fields fill_geom_args / the FiLM prep read
-    ra.B = a->B;
-    ra.H = a->H;
-    ra.W = a->W;
-    ra.N = a->N;
-    ra.cam = a->cam;
-    ra.focal = a->focal;
-    ra.near_ = a->near_;
-    ra.far_ = a->far_;
-    ra.styles = a->styles;
-    ra.pix_x = a->pix_x;
-    ra.pix_y = a->pix_y;
-    ra.t_vals = a->t_vals;
-    ra.t_rand = a->t_rand;
-    ra.t_rand_per_sample = a->t_rand_per_sample;
-    ra.offset_sampling = a->offset_sampling;
-    ra.z_normalize = a->z_normalize;
-    ra.prepacked = a->prepacked;
     GeomArgs g;
-    fill_geom_args(&ra, w->bound, g);
+    fill_geom_args(a, 0, w->bound, g);       // the network's view direction is not read
     const bool composite = a->eikonal || a->normal || a->depth || a->xyz || a->mask;
-    int rc;
     if ((rc = launch_geom_points(g, pnet, zd, st))) return rc;
     if ((rc = launch_grad_gather(w, pnet, gd, a->B, M, Mp, st))) return rc;
-    if ((rc = launch_xprep_ngp(w, &ra, ws + o_x, film, st))) return rc;
+    if ((rc = launch_xprep_ngp(w, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
+        return rc;
     const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
     if ((rc = launch_gfield_ngp(w, xws, film, gd, sdf, gnet, a->B, M, Mp, st))) return rc;
     if (!composite) return SDFR_OK;

@@ -852,15 +852,21 @@ class Generator(nn.Module):
         return self.renderer.mlp_init_pass(cam_poses, focals, near, far, styles=latent[0],
                                            t_rand=t_rand)
 
+    def _renderer_latent(self, styles, truncation=1, truncation_latent=None,
+                         input_is_latent=False):
+        """The renderer's latent [B,256] of ``styles``: the mapping network and truncation
+        of ``forward`` (``styles_and_noise_forward``)."""
+        latent = self.styles_and_noise_forward(styles, None, truncation, truncation_latent,
+                                               input_is_latent)
+        return latent[0][:, 0] if input_is_latent else latent[0]
+
     def query_field(self, points, styles, viewdirs=None, truncation=1, truncation_latent=None,
                     input_is_latent=False, return_rgb=True):
         """The renderer's field at ``points`` [B,M,3] (network coordinates) for the faces
         of ``styles``: the mapping network and truncation of ``forward``
         (``styles_and_noise_forward``), then ``VolumeFeatureRenderer.query`` ->
         ``(sdf [B,M], rgb [B,M,3] | None)``."""
-        latent = self.styles_and_noise_forward(styles, None, truncation, truncation_latent,
-                                               input_is_latent)
-        lat0 = latent[0][:, 0] if input_is_latent else latent[0]
+        lat0 = self._renderer_latent(styles, truncation, truncation_latent, input_is_latent)
         return self.renderer.query(points, lat0, viewdirs=viewdirs, return_rgb=return_rgb)
 
     def query_field_gradient(self, points, styles, truncation=1, truncation_latent=None,
@@ -868,9 +874,7 @@ class Generator(nn.Module):
         """The SDF and its gradient at ``points`` [B,M,3] (network coordinates) for the
         faces of ``styles``: the mapping network and truncation of ``query_field``, then
         ``VolumeFeatureRenderer.query_gradient`` -> ``(sdf [B,M], grad [B,M,3])``."""
-        latent = self.styles_and_noise_forward(styles, None, truncation, truncation_latent,
-                                               input_is_latent)
-        lat0 = latent[0][:, 0] if input_is_latent else latent[0]
+        lat0 = self._renderer_latent(styles, truncation, truncation_latent, input_is_latent)
         return self.renderer.query_gradient(points, lat0, normalize=normalize,
                                             chunk_points=chunk_points)
 
@@ -880,9 +884,7 @@ class Generator(nn.Module):
         network and truncation of ``query_field_gradient``, then
         ``VolumeFeatureRenderer.render_geometry`` (``kw``: t_rand, want, normalize,
         chunk_points) -> ``Geometry``.  Not part of the forward graph cache."""
-        latent = self.styles_and_noise_forward(styles, None, truncation, truncation_latent,
-                                               input_is_latent)
-        lat0 = latent[0][:, 0] if input_is_latent else latent[0]
+        lat0 = self._renderer_latent(styles, truncation, truncation_latent, input_is_latent)
         return self.renderer.render_geometry(cam_poses, focals, near, far, lat0, **kw)
 
     def forward(self, styles, cam_poses, focals, near=0.88, far=1.12, return_latents=False,

@@ -245,8 +245,11 @@ def workspace_bytes(kind: int, B: int, H: int, W: int, N: int, num_levels: int) 
 FORWARD_FN = ("sdfr_render_ngp_forward", "sdfr_render_siren_forward", "sdfr_render_fc_forward")
 
 
-def _render_outputs(B, H, W, N, dev, output_features, return_sdf, return_xyz, empty):
-    z = lambda: empty(0, device=dev)  # noqa: E731
+def _render_outputs(B, H, W, N, dev, output_features, return_sdf, return_xyz, empty,
+                    absent_none=False):
+    """(rgb, features, sdf, mask, xyz) of a render; an output that is not asked for is an
+    empty tensor (an op returns tensors), or None with ``absent_none``."""
+    z = (lambda: None) if absent_none else (lambda: empty(0, device=dev))  # noqa: E731
     return (empty(B, 3, H, W, device=dev),
             empty(B, 256, H, W, device=dev) if output_features else z(),
             empty(B, H, W, N, 1, device=dev) if return_sdf else z(),

@@ -278,6 +278,18 @@ def _per_face(x, B, device):
     return (t.expand(B) if t.numel() == 1 else t).contiguous()
 
 
+def _unit(x, dim):
+    """``x / max(|x|, 1e-20)`` along ``dim`` (a zero vector stays zero)."""
+    return x / x.norm(dim=dim, keepdim=True).clamp_min(1e-20)
+
+
+def _workspace(ws, need, device):
+    """``ws`` if it holds ``need`` bytes, else a new one that does."""
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
 # What VolumeFeatureRenderer.render_geometry returns: NCHW maps and the per-sample SDF and
 # eikonal term in forward's layout; fields that were not asked for are None.
 Geometry = namedtuple("Geometry", ("normal", "depth", "xyz", "mask", "sdf", "eikonal"))
@@ -381,11 +393,26 @@ class VolumeFeatureRenderer(nn.Module):
     def sdf_activation(self, input):
         return torch.sigmoid(input / self.sigmoid_beta) / self.sigmoid_beta
 
-    def volume_integration(self, raw, z_vals, rays_d, pts, return_eikonal=False):
+    def compositing_weights(self, sdf, z_vals, rays_d, noise=0.):
+        """The weights [B,H,W,N,1] of the front-to-back composite (sdf_model.py:236-301)
+        from the network's per-sample fourth output [B,H,W,N,1]: the SDF, or without one
+        the raw density that ``noise`` is added to.  The one place that turns alpha into
+        weights; autograd follows the caller's grad mode."""
         dists = z_vals[..., 1:] - z_vals[..., :-1]
         rays_d_norm = torch.norm(rays_d.unsqueeze(self.samples_dim), dim=self.channel_dim)
         dists = torch.cat([dists, self.inf.expand(rays_d_norm.shape)], self.channel_dim)
         dists = dists * rays_d_norm
+        density = self.sdf_activation(-sdf) if self.with_sdf else F.softplus(sdf + noise)
+        sigma = 1 - torch.exp(-density * dists.unsqueeze(self.channel_dim))
+        first = torch.ones_like(torch.index_select(sigma, self.samples_dim, self.zero_idx))
+        visibility = torch.cumprod(torch.cat([first, 1. - sigma + 1e-10], self.samples_dim),
+                                   self.samples_dim)[..., :-1, :]
+        weights = sigma * visibility
+        if self.force_background:
+            weights[..., -1, :] = 1 - weights[..., :-1, :].sum(self.samples_dim)
+        return weights
+
+    def volume_integration(self, raw, z_vals, rays_d, pts, return_eikonal=False):
         if self.output_features:
             rgb, sdf, features = torch.split(raw, [3, 1, self.feature_out_size],
                                              dim=self.channel_dim)
@@ -394,20 +421,11 @@ class VolumeFeatureRenderer(nn.Module):
         noise = 0.
         if self.raw_noise_std > 0.:
             noise = torch.randn_like(sdf) * self.raw_noise_std
-        if self.with_sdf:
-            sigma = self.sdf_activation(-sdf)
-            eikonal_term = self.get_eikonal_term(pts, sdf) if return_eikonal else None
-            sigma = 1 - torch.exp(-sigma * dists.unsqueeze(self.channel_dim))
-        else:
-            eikonal_term = None
-            sigma = 1 - torch.exp(-F.softplus(sdf + noise) * dists.unsqueeze(self.channel_dim))
-        first = torch.ones_like(torch.index_select(sigma, self.samples_dim, self.zero_idx))
-        visibility = torch.cumprod(torch.cat([first, 1. - sigma + 1e-10], self.samples_dim),
-                                   self.samples_dim)[..., :-1, :]
-        weights = sigma * visibility
+        eikonal_term = None
+        if self.with_sdf and return_eikonal:
+            eikonal_term = self.get_eikonal_term(pts, sdf)
+        weights = self.compositing_weights(sdf, z_vals, rays_d, noise)
         sdf_out = sdf if self.return_sdf else None
-        if self.force_background:
-            weights[..., -1, :] = 1 - weights[..., :-1, :].sum(self.samples_dim)
         rgb_map = -1 + 2 * torch.sum(weights * torch.sigmoid(rgb), self.samples_dim)
         feature_map = (torch.sum(weights * features, self.samples_dim)
                        if self.output_features else None)
@@ -428,7 +446,6 @@ class VolumeFeatureRenderer(nn.Module):
         return torch.rand(shape, device=device)
 
     def render_rays(self, ray_batch, styles=None, return_eikonal=False, t_rand=None):
-        batch, h, w, _ = ray_batch.shape
         split = [3, 3, 2]
         if ray_batch.shape[-1] > 8:
             rays_o, rays_d, bounds, viewdirs = torch.split(ray_batch, split + [3], dim=-1)
@@ -436,55 +453,64 @@ class VolumeFeatureRenderer(nn.Module):
             rays_o, rays_d, bounds = torch.split(ray_batch, split, dim=-1)
             viewdirs = None
         near, far = torch.split(bounds, [1, 1], dim=-1)
-        z_vals = near * (1. - self.t_vals) + far * self.t_vals
-        if self.perturb > 0.:
-            if self.offset_sampling:
-                upper = torch.cat([z_vals[..., 1:], far], -1)
-                lower = z_vals.detach()
-                if t_rand is None:
-                    t_rand = self._draw_t_rand((batch, h, w), z_vals.device)
-                t_rand = t_rand.to(z_vals.device).reshape(batch, h, w, 1)
-            else:
-                mids = .5 * (z_vals[..., 1:] + z_vals[..., :-1])
-                upper = torch.cat([mids, z_vals[..., -1:]], -1)
-                lower = torch.cat([z_vals[..., :1], mids], -1)
-                if t_rand is None:
-                    t_rand = self._draw_t_rand(z_vals.shape, z_vals.device)
-                t_rand = t_rand.to(z_vals.device).reshape(z_vals.shape)
-            z_vals = lower + (upper - lower) * t_rand
-        pts = rays_o.unsqueeze(3) + rays_d.unsqueeze(3) * z_vals.unsqueeze(-1)
-        if return_eikonal:
-            pts.requires_grad = True
-        normalized_pts = pts * 2 / ((far - near).unsqueeze(3)) if self.z_normalize else pts
+        z_vals, pts, normalized_pts = self.sample_points(
+            rays_o, rays_d, near, far, t_rand, self._stratify(), pts_grad=return_eikonal)
         raw = self.run_network(normalized_pts, viewdirs, styles=styles)
         return self.volume_integration(raw, z_vals, rays_d, pts, return_eikonal=return_eikonal)
 
-    def render(self, focal, c2w, near, far, styles, c2w_staticcam=None, return_eikonal=False,
-               t_rand=None):
+    def camera_rays(self, focal, c2w, near, far):
+        """``rays_o, rays_d, viewdirs`` (unit length) [B,H,W,3] and ``near, far`` [B,H,W,1]."""
         rays_o, rays_d, viewdirs = self.get_rays(focal, c2w)
         viewdirs = viewdirs / torch.norm(viewdirs, dim=-1, keepdim=True)
         near = near.unsqueeze(-1) * torch.ones_like(rays_d[..., :1])
         far = far.unsqueeze(-1) * torch.ones_like(rays_d[..., :1])
+        return rays_o, rays_d, viewdirs, near, far
+
+    def _stratify(self):
+        """The renderer's own mode of ``sample_points``."""
+        if self.perturb > 0.:
+            return "offset" if self.offset_sampling else "mid"
+        return None
+
+    def sample_points(self, rays_o, rays_d, near, far, t_rand, stratify, pts_grad=False):
+        """``z_vals`` [B,H,W,N], the samples ``pts`` [B,H,W,N,3] and what the network sees
+        of them: the one place that knows how samples are placed along a ray.
+        ``stratify``: None (the ``t_vals`` depths), "offset" (one shift per ray, up to the
+        next depth) or "mid" (one draw per sample between the mid-points); ``t_rand`` is
+        drawn in that shape when it is None.  ``pts_grad``: ``pts`` requires grad, for the
+        eikonal term."""
+        z_vals = near * (1. - self.t_vals) + far * self.t_vals
+        if stratify is not None:
+            if stratify == "offset":
+                upper = torch.cat([z_vals[..., 1:], far], -1)
+                lower = z_vals.detach()
+                drawn, shape = z_vals.shape[:-1], z_vals.shape[:-1] + (1,)
+            else:
+                mids = .5 * (z_vals[..., 1:] + z_vals[..., :-1])
+                upper = torch.cat([mids, z_vals[..., -1:]], -1)
+                lower = torch.cat([z_vals[..., :1], mids], -1)
+                drawn = shape = z_vals.shape
+            if t_rand is None:
+                t_rand = self._draw_t_rand(drawn, z_vals.device)
+            z_vals = lower + (upper - lower) * t_rand.to(z_vals.device).reshape(shape)
+        pts = rays_o.unsqueeze(3) + rays_d.unsqueeze(3) * z_vals.unsqueeze(-1)
+        if pts_grad:
+            pts.requires_grad = True
+        normalized_pts = pts * 2 / ((far - near).unsqueeze(3)) if self.z_normalize else pts
+        return z_vals, pts, normalized_pts
+
+    def render(self, focal, c2w, near, far, styles, c2w_staticcam=None, return_eikonal=False,
+               t_rand=None):
+        rays_o, rays_d, viewdirs, near, far = self.camera_rays(focal, c2w, near, far)
         rays = torch.cat([rays_o, rays_d, near, far], -1)
         rays = torch.cat([rays, viewdirs], -1).float()
         return self.render_rays(rays, styles=styles, return_eikonal=return_eikonal,
                                 t_rand=t_rand)
 
     def mlp_init_pass(self, cam_poses, focal, near, far, styles=None, t_rand=None):
-        rays_o, rays_d, viewdirs = self.get_rays(focal, cam_poses)
-        viewdirs = viewdirs / torch.norm(viewdirs, dim=-1, keepdim=True)
-        near = near.unsqueeze(-1) * torch.ones_like(rays_d[..., :1])
-        far = far.unsqueeze(-1) * torch.ones_like(rays_d[..., :1])
-        z_vals = near * (1. - self.t_vals) + far * self.t_vals
-        mids = .5 * (z_vals[..., 1:] + z_vals[..., :-1])
-        upper = torch.cat([mids, z_vals[..., -1:]], -1)
-        lower = torch.cat([z_vals[..., :1], mids], -1)
-        if t_rand is None:
-            t_rand = self._draw_t_rand(z_vals.shape, z_vals.device)
-        t_rand = t_rand.to(z_vals.device).reshape(z_vals.shape)
-        z_vals = lower + (upper - lower) * t_rand
-        pts = rays_o.unsqueeze(3) + rays_d.unsqueeze(3) * z_vals.unsqueeze(-1)
-        normalized_pts = pts * 2 / ((far - near).unsqueeze(3)) if self.z_normalize else pts
+        rays_o, rays_d, viewdirs, near, far = self.camera_rays(focal, cam_poses, near, far)
+        # always one draw per sample, whatever perturb and offset_sampling say
+        _, pts, normalized_pts = self.sample_points(rays_o, rays_d, near, far, t_rand, "mid")
         raw = self.run_network(normalized_pts, viewdirs, styles=styles)
         _, sdf = torch.split(raw[..., :4], [3, 1], dim=-1)
         sdf = sdf.squeeze(-1)
@@ -503,23 +529,27 @@ class VolumeFeatureRenderer(nn.Module):
             return 2
         return None
 
-    def _fused_ok(self, cam_poses, styles, return_eikonal):
-        if not self.use_fused:
-            return False
-        kind = self._net_kind()
-        if kind is None:
-            return False
-        if kind and (self.field_precision != "f16x3" or self.network.D != 8 or
-                     len(self.network.pts_linears) != (8 if kind == 1 else 7)):
-            return False
-        if return_eikonal or not cam_poses.is_cuda or styles is None:
+    def _fused_inputs_ok(self, x, styles, no_grad_on=()):
+        """What every fused call needs (the network's kind is the caller's to check first):
+        ``use_fused``, ``x`` on the GPU, styles [B,256] for a 256-wide network, and under
+        grad mode nothing that requires grad among styles, ``no_grad_on``, parameters."""
+        if not self.use_fused or not x.is_cuda or styles is None:
             return False
         if styles.dim() != 2 or styles.shape[1] != 256 or self.network.W != 256:
             return False
         if torch.is_grad_enabled() and (styles.requires_grad or any(
-                p.requires_grad for p in self.parameters())):
+                t.requires_grad for t in (*no_grad_on, *self.parameters()))):
             return False
         return True
+
+    def _fused_ok(self, cam_poses, styles, return_eikonal):
+        kind = self._net_kind()
+        if kind is None or return_eikonal:
+            return False
+        if kind and (self.field_precision != "f16x3" or self.network.D != 8 or
+                     len(self.network.pts_linears) != (8 if kind == 1 else 7)):
+            return False
+        return self._fused_inputs_ok(cam_poses, styles)
 
     def _weight_tensors(self, kind):
         """The network's tensors in the order of ops.weights_struct / sdfr::render_fused
@@ -574,6 +604,34 @@ class VolumeFeatureRenderer(nn.Module):
             if not p.is_contiguous() or p.dtype != torch.float32:
                 raise RuntimeError("fused ngp renderer needs contiguous fp32 parameters")
 
+    def _fused_inputs(self, cam_poses, focal, near, far, styles, t_rand):
+        """A camera call's inputs as the library takes them (contiguous fp32 on the cameras'
+        device): ``cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals``.
+        ``t_rand`` is None without ``perturb``, else [B,H,W] or (``per_sample`` = 1)
+        [B,H,W,N], drawn here when none was given."""
+        dev = cam_poses.device
+        B = cam_poses.shape[0]
+        cam = cam_poses.detach().float().contiguous()
+        focal = _per_face(focal, B, dev)
+        near = _per_face(near, B, dev)
+        far = _per_face(far, B, dev)
+        styles = styles.detach().float().contiguous()
+        per_sample = 0
+        if self.perturb > 0:
+            shape = (B, self.out_im_res, self.out_im_res)
+            if not self.offset_sampling:
+                shape += (self.N_samples,)
+                per_sample = 1
+            if t_rand is None:
+                t_rand = self._draw_t_rand(shape, dev)
+            t_rand = t_rand.to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
+        else:
+            t_rand = None
+        pix_x = self.i[0, 0, :].contiguous()
+        pix_y = self.j[0, :, 0].contiguous()
+        t_vals = self.t_vals.reshape(-1).contiguous()
+        return cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals
+
     def fused_forward(self, cam_poses, focal, near, far, styles, t_rand=None, encode_only=False,
                       styles_event=None, feat_mod=None):
         """The whole ngp render on libsdfr (no autograd).  Returns the same tuple
@@ -594,20 +652,8 @@ class VolumeFeatureRenderer(nn.Module):
         B = cam_poses.shape[0]
         H = W = self.out_im_res
         N = self.N_samples
-        cam = cam_poses.detach().float().contiguous()
-        focal = _per_face(focal, B, dev)
-        near = _per_face(near, B, dev)
-        far = _per_face(far, B, dev)
-        styles = styles.detach().float().contiguous()
-        per_sample = 0
-        if self.perturb > 0:
-            shape = (B, H, W) if self.offset_sampling else (B, H, W, N)
-            if t_rand is None:
-                t_rand = self._draw_t_rand(shape, dev)
-            t_rand = t_rand.to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
-            per_sample = 0 if self.offset_sampling else 1
-        else:
-            t_rand = None
+        cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals = \
+            self._fused_inputs(cam_poses, focal, near, far, styles, t_rand)
         noise = None
         if not self.with_sdf and self.raw_noise_std > 0:
             noise = torch.randn(B, H, W, N, device=dev) * self.raw_noise_std
@@ -620,9 +666,6 @@ class VolumeFeatureRenderer(nn.Module):
                              f"got {self.field_precision!r}")
         if kind and encode_only:
             raise RuntimeError("only the ngp renderer has a hash-grid encode stage")
-        pix_x = self.i[0, 0, :].contiguous()
-        pix_y = self.j[0, :, 0].contiguous()
-        t_vals = self.t_vals.reshape(-1).contiguous()
         flags = dict(
             t_rand_per_sample=per_sample, offset_sampling=int(self.offset_sampling),
             static_viewdirs=int(bool(self.static_viewdirs)), z_normalize=int(self.z_normalize),
@@ -641,18 +684,15 @@ class VolumeFeatureRenderer(nn.Module):
                 kind, self._weight_tensors(kind), cam, focal, near, far, styles, t_rand, noise,
                 pix_x, pix_y, t_vals, prepacked, fs, is_, [flags[k] for k in ops.RENDER_FLAGS],
                 H, W, N)
-            rgb, features, sdf, mask, xyz = (None if t.numel() == 0 else t for t in out)
+            rgb, features, sdf, mask, xyz = map(ops._none_if_empty, out)
             return rgb, features, sdf, mask, xyz, None
         # with events (stage timing, the styles hand-off of Generator.forward), the
         # decoder-layout feature store or the encode stage alone: the library directly
-        rgb = torch.empty(B, 3, H, W, device=dev)
-        features = (torch.empty(B, 256, H, W, device=dev)
-                    if self.output_features and feat_mod is None else None)
+        rgb, features, sdf, mask, xyz = ops._render_outputs(
+            B, H, W, N, dev, self.output_features and feat_mod is None, self.return_sdf,
+            self.return_xyz, torch.empty, absent_none=True)
         feat_split = (torch.empty(B, H, W, 32, 2, 8, device=dev, dtype=torch.float16)
                       if feat_mod is not None else None)
-        sdf = torch.empty(B, H, W, N, 1, device=dev) if self.return_sdf else None
-        xyz = torch.empty(B, 3, H, W, device=dev) if self.return_xyz else None
-        mask = torch.empty(B, 1, H, W, device=dev) if self.return_xyz else None
         num_levels = self.network.encoder.num_levels if kind == 0 else 0
         ws = torch.empty(ops.workspace_bytes(kind, B, H, W, N, num_levels), dtype=torch.uint8,
                          device=dev)
@@ -706,15 +746,9 @@ class VolumeFeatureRenderer(nn.Module):
     def _query_fused_ok(self, points, styles):
         """The rule of ``_fused_ok`` for a point query (the fused query exists for the
         ngp network on the f16x3 field kernel only)."""
-        if not self.use_fused or self._net_kind() != 0 or self.field_precision != "f16x3":
+        if self._net_kind() != 0 or self.field_precision != "f16x3":
             return False
-        if not points.is_cuda or styles.dim() != 2 or styles.shape[1] != 256 \
-                or self.network.W != 256:
-            return False
-        if torch.is_grad_enabled() and (styles.requires_grad or points.requires_grad or any(
-                p.requires_grad for p in self.parameters())):
-            return False
-        return True
+        return self._fused_inputs_ok(points, styles, no_grad_on=(points,))
 
     def query(self, points, styles, viewdirs=None, return_rgb=True, chunk_groups=None):
         """The field itself at arbitrary points: ``(sdf [B,M], rgb [B,M,3] | None)``.
@@ -782,30 +816,42 @@ class VolumeFeatureRenderer(nn.Module):
         L = _lib.lib()
         prepacked = self._prepacked(0, pts)
         w = self._weight_struct(0)
-        whole = R <= chunk_groups
-        ws = None
-        for r0 in range(0, R, chunk_groups):
-            r1 = min(R, r0 + chunk_groups)
-            # a chunk is a call of its own on contiguous [B,r,..] tensors
-            c_pts = pts if whole else pts[:, r0:r1].contiguous()
-            c_dirs = dirs[:, r0:r1].float().contiguous()
-            c_sdf = sdf if whole else torch.empty(B, r1 - r0, N, device=dev)
-            c_rgb = rgb if whole or rgb is None else torch.empty(B, r1 - r0, N, 3, device=dev)
-            need = L.sdfr_query_ngp_workspace_bytes(B, r1 - r0, N)
-            if ws is None or ws.numel() < need:
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+        def call(r, ins, outs, ws):
             a = _lib.NgpQueryArgs(
-                B=B, R=r1 - r0, N=N, points=_lib.ptr(c_pts), dirs=_lib.ptr(c_dirs),
-                styles=_lib.ptr(styles), sdf=_lib.ptr(c_sdf), rgb=_lib.ptr(c_rgb),
+                B=B, R=r, N=N, points=_lib.ptr(ins[0]), dirs=_lib.ptr(ins[1]),
+                styles=_lib.ptr(styles), sdf=_lib.ptr(outs[0]), rgb=_lib.ptr(outs[1]),
                 workspace=_lib.ptr(ws), workspace_bytes=ws.numel(),
                 prepacked=_lib.ptr(prepacked))
             _lib.check(L.sdfr_query_ngp_forward(ctypes.byref(w), ctypes.byref(a),
                                                 _lib.stream_of(pts)), "sdfr_query_ngp_forward")
-            if not whole:
-                sdf[:, r0:r1] = c_sdf
-                if rgb is not None:
-                    rgb[:, r0:r1] = c_rgb
+
+        self._chunked_calls(R, chunk_groups, (pts, dirs.float()), (sdf, rgb),
+                            lambda r: L.sdfr_query_ngp_workspace_bytes(B, r, N), call)
         return sdf, rgb
+
+    @staticmethod
+    def _chunked_calls(total, chunk, ins, outs, workspace_bytes, call):
+        """``call(n, ins, outs, ws)`` on at most ``chunk`` of the ``total`` entries along
+        dim 1 of the [B,total,..] tensors ``ins`` and ``outs`` (an output may be None) at a
+        time.  A chunk is a call of its own on contiguous tensors: the caller's own when
+        one chunk is the whole, else copies in and out.  The workspace grows to
+        ``workspace_bytes(n)``; the last one is returned."""
+        whole = total <= chunk
+        ws = None
+        for i0 in range(0, total, chunk):
+            i1 = min(total, i0 + chunk)
+            c_ins = [(t if whole else t[:, i0:i1]).contiguous() for t in ins]
+            c_outs = [t if whole or t is None else
+                      torch.empty((t.shape[0], i1 - i0) + t.shape[2:], device=t.device)
+                      for t in outs]
+            ws = _workspace(ws, workspace_bytes(i1 - i0), ins[0].device)
+            call(i1 - i0, c_ins, c_outs, ws)
+            if not whole:
+                for t, c in zip(outs, c_outs):
+                    if t is not None:
+                        t[:, i0:i1] = c
+        return ws
 
     # ---------------------------------------------------------------- SDF gradient
     # Points per library call of the fused gradient.  The workspace is 512 bytes per
@@ -858,10 +904,7 @@ class VolumeFeatureRenderer(nn.Module):
                 sdf = raw[..., 3]
                 grad, = torch.autograd.grad(sdf.sum(), pts)
             sdf = sdf.detach()
-        if normalize:
-            n = grad.norm(dim=-1, keepdim=True)
-            grad = grad / n.clamp_min(1e-20)
-        return sdf, grad
+        return sdf, (_unit(grad, -1) if normalize else grad)
 
     def _fused_gradient(self, points, styles, chunk_points=None, encode_only=False):
         """``sdfr_query_ngp_grad`` on ``points`` [B,M,3] in calls of at most
@@ -881,26 +924,17 @@ class VolumeFeatureRenderer(nn.Module):
         L = _lib.lib()
         prepacked = self._prepacked(0, pts)
         w = self._weight_struct(0)
-        whole = M <= chunk_points
-        ws = None
-        for m0 in range(0, M, chunk_points):
-            m1 = min(M, m0 + chunk_points)
-            # a chunk is a call of its own on contiguous [B,m,..] tensors
-            c_pts = pts if whole else pts[:, m0:m1].contiguous()
-            c_sdf = sdf if whole else torch.empty(B, m1 - m0, device=dev)
-            c_grad = grad if whole else torch.empty(B, m1 - m0, 3, device=dev)
-            need = L.sdfr_query_ngp_grad_workspace_bytes(B, m1 - m0)
-            if ws is None or ws.numel() < need:
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+        def call(m, ins, outs, ws):
             a = _lib.NgpGradArgs(
-                B=B, M=m1 - m0, points=_lib.ptr(c_pts), styles=_lib.ptr(styles),
-                sdf=_lib.ptr(c_sdf), grad=_lib.ptr(c_grad), workspace=_lib.ptr(ws),
+                B=B, M=m, points=_lib.ptr(ins[0]), styles=_lib.ptr(styles),
+                sdf=_lib.ptr(outs[0]), grad=_lib.ptr(outs[1]), workspace=_lib.ptr(ws),
                 workspace_bytes=ws.numel(), prepacked=_lib.ptr(prepacked))
             _lib.check(L.sdfr_query_ngp_grad(ctypes.byref(w), ctypes.byref(a),
                                              _lib.stream_of(pts)), "sdfr_query_ngp_grad")
-            if not whole:
-                sdf[:, m0:m1] = c_sdf
-                grad[:, m0:m1] = c_grad
+
+        ws = self._chunked_calls(M, chunk_points, (pts,), (sdf, grad),
+                                 lambda m: L.sdfr_query_ngp_grad_workspace_bytes(B, m), call)
         if encode_only:
             # the workspace starts with the gather's output [B][Mp][4][32], Mp = M up to 8
             Mp = (M + 7) // 8 * 8
@@ -951,8 +985,7 @@ class VolumeFeatureRenderer(nn.Module):
         else:
             out = self._module_geometry(cam_poses, focal, near, far, styles, t_rand, want)
         if normalize and out.get("normal") is not None:
-            n = out["normal"].norm(dim=1, keepdim=True)
-            out["normal"] = out["normal"] / n.clamp_min(1e-20)
+            out["normal"] = _unit(out["normal"], 1)
         return Geometry(**{k: out.get(k) for k in self.GEOMETRY_FIELDS})
 
     def _fused_geometry(self, cam_poses, focal, near, far, styles, t_rand, want, chunk_points):
@@ -962,23 +995,8 @@ class VolumeFeatureRenderer(nn.Module):
         B = cam_poses.shape[0]
         H = W = self.out_im_res
         N = self.N_samples
-        cam = cam_poses.detach().float().contiguous()
-        focal = _per_face(focal, B, dev)
-        near = _per_face(near, B, dev)
-        far = _per_face(far, B, dev)
-        styles = styles.detach().float().contiguous()
-        per_sample = 0
-        if self.perturb > 0:
-            shape = (B, H, W) if self.offset_sampling else (B, H, W, N)
-            if t_rand is None:
-                t_rand = self._draw_t_rand(shape, dev)
-            t_rand = t_rand.to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
-            per_sample = 0 if self.offset_sampling else 1
-        else:
-            t_rand = None
-        pix_x = self.i[0, 0, :].contiguous()
-        pix_y = self.j[0, :, 0].contiguous()
-        t_vals = self.t_vals.reshape(-1).contiguous()
+        cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals = \
+            self._fused_inputs(cam_poses, focal, near, far, styles, t_rand)
         shapes = {"sdf": (B, H, W, N), "eikonal": (B, H, W, N, 3), "normal": (B, 3, H, W),
                   "depth": (B, 1, H, W), "xyz": (B, 3, H, W), "mask": (B, 1, H, W)}
         out = {k: torch.empty(shapes[k], device=dev) for k in want}
@@ -1011,9 +1029,8 @@ class VolumeFeatureRenderer(nn.Module):
                 c_rand = None
                 if t_rand is not None:
                     c_rand = t_rand[b0:b1, y0:y1].contiguous()
-                need = L.sdfr_render_ngp_geometry_workspace_bytes(b1 - b0, y1 - y0, W, N)
-                if ws is None or ws.numel() < need:
-                    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                ws = _workspace(ws, L.sdfr_render_ngp_geometry_workspace_bytes(
+                    b1 - b0, y1 - y0, W, N), dev)
                 c_y = pix_y[y0:y1]
                 a = _lib.NgpGeometryArgs(
                     B=b1 - b0, H=y1 - y0, W=W, N=N, cam=_lib.ptr(cam[b0:b1]),
@@ -1037,58 +1054,17 @@ class VolumeFeatureRenderer(nn.Module):
             out["sdf"] = out["sdf"].unsqueeze(-1)
         return out
 
-    def _geometry_weights(self, sdf, z_vals, rays_d):
-        """The compositing weights [B,H,W,N,1] of ``volume_integration`` from a per-sample
-        SDF [B,H,W,N,1] (the geometry render's module path; no autograd graph)."""
-        with torch.no_grad():
-            dists = z_vals[..., 1:] - z_vals[..., :-1]
-            rays_d_norm = torch.norm(rays_d.unsqueeze(self.samples_dim), dim=self.channel_dim)
-            dists = torch.cat([dists, self.inf.expand(rays_d_norm.shape)], self.channel_dim)
-            dists = dists * rays_d_norm
-            sigma = self.sdf_activation(-sdf)
-            sigma = 1 - torch.exp(-sigma * dists.unsqueeze(self.channel_dim))
-            first = torch.ones_like(torch.index_select(sigma, self.samples_dim, self.zero_idx))
-            visibility = torch.cumprod(torch.cat([first, 1. - sigma + 1e-10], self.samples_dim),
-                                       self.samples_dim)[..., :-1, :]
-            weights = sigma * visibility
-            if self.force_background:
-                weights[..., -1, :] = 1 - weights[..., :-1, :].sum(self.samples_dim)
-        return weights
-
     def _module_geometry(self, cam_poses, focal, near, far, styles, t_rand, want):
-        """``render_geometry`` op by op: the rays and samples of ``render`` /
-        ``render_rays``, the gradient by autograd on detached inputs."""
+        """``render_geometry`` op by op: the rays, samples and weights of ``render``, the
+        gradient by autograd on detached inputs."""
         cam_poses, focal, near, far = (t.detach() for t in (cam_poses, focal, near, far))
         styles = styles.detach() if styles is not None else None
         with torch.no_grad():
-            rays_o, rays_d, viewdirs = self.get_rays(focal, cam_poses)
-            viewdirs = viewdirs / torch.norm(viewdirs, dim=-1, keepdim=True)
-            near = near.unsqueeze(-1) * torch.ones_like(rays_d[..., :1])
-            far = far.unsqueeze(-1) * torch.ones_like(rays_d[..., :1])
-            rays = torch.cat([rays_o, rays_d, near, far, viewdirs], -1).float()
-            rays_o, rays_d, bounds, viewdirs = torch.split(rays, [3, 3, 2, 3], dim=-1)
-            near, far = torch.split(bounds, [1, 1], dim=-1)
-            batch, h, w, _ = rays.shape
-            z_vals = near * (1. - self.t_vals) + far * self.t_vals
-            if self.perturb > 0.:
-                if self.offset_sampling:
-                    upper = torch.cat([z_vals[..., 1:], far], -1)
-                    lower = z_vals
-                    if t_rand is None:
-                        t_rand = self._draw_t_rand((batch, h, w), z_vals.device)
-                    t_rand = t_rand.to(z_vals.device).reshape(batch, h, w, 1)
-                else:
-                    mids = .5 * (z_vals[..., 1:] + z_vals[..., :-1])
-                    upper = torch.cat([mids, z_vals[..., -1:]], -1)
-                    lower = torch.cat([z_vals[..., :1], mids], -1)
-                    if t_rand is None:
-                        t_rand = self._draw_t_rand(z_vals.shape, z_vals.device)
-                    t_rand = t_rand.to(z_vals.device).reshape(z_vals.shape)
-                z_vals = lower + (upper - lower) * t_rand
-            pts = rays_o.unsqueeze(3) + rays_d.unsqueeze(3) * z_vals.unsqueeze(-1)
+            rays_o, rays_d, viewdirs, near, far = (
+                t.float() for t in self.camera_rays(focal, cam_poses, near, far))
         with torch.enable_grad():
-            pts = pts.requires_grad_(True)
-            normalized_pts = pts * 2 / ((far - near).unsqueeze(3)) if self.z_normalize else pts
+            z_vals, pts, normalized_pts = self.sample_points(
+                rays_o, rays_d, near, far, t_rand, self._stratify(), pts_grad=True)
             raw = self.run_network(normalized_pts, viewdirs, styles=styles)
             sdf = raw[..., 3:4]
             eikonal, = autograd.grad(outputs=sdf, inputs=pts, grad_outputs=torch.ones_like(sdf))
@@ -1099,8 +1075,8 @@ class VolumeFeatureRenderer(nn.Module):
         if "eikonal" in want:
             out["eikonal"] = eikonal
         if any(k in want for k in ("normal", "depth", "xyz", "mask")):
-            weights = self._geometry_weights(sdf, z_vals, rays_d)
             with torch.no_grad():
+                weights = self.compositing_weights(sdf, z_vals, rays_d)
                 maps = {"normal": lambda: torch.sum(weights * eikonal, self.samples_dim),
                         "depth": lambda: torch.sum(weights * z_vals.unsqueeze(-1),
                                                    self.samples_dim),

@@ -1,8 +1,10 @@
 """CPU: the geometry render's C-ABI argument checks and workspace size
 (sdfr_render_ngp_geometry, include/sdfr.h) and VolumeFeatureRenderer.render_geometry /
 Generator.render_geometry on the op-by-op path: against the reference's SIREN eikonal
-fixture, against forward(return_eikonal=True), and on a stub network with a linear SDF."""
+fixture, against forward(return_eikonal=True) (also over every sampling flag on a small
+SIREN renderer), and on a stub network with a linear SDF."""
 import ctypes
+import itertools
 
 import numpy as np
 import pytest
@@ -314,3 +316,34 @@ def test_render_geometry_grad_mode_and_argument_errors(sdfr):
     plain = _stub_renderer(sdfr, res, N, no_sdf=True)
     with pytest.raises(ValueError, match="no_sdf"):
         plain.render_geometry(ext, focal, near, far, lat)
+
+
+def test_render_geometry_shares_forward_samples_and_weights(sdfr):
+    """5. A small SIREN renderer over perturb x no_offset_sampling x force_background x
+    no_z_normalize, t_rand given: render_geometry's sdf, eikonal, xyz and mask are
+    forward(return_eikonal=True)'s bit for bit -- the two paths place their samples and
+    form their weights in the same code."""
+    B, res, N, style_dim = 2, 4, 3, 32
+    for perturb, no_offset, background, no_z in itertools.product((0, 1), repeat=4):
+        flags = dict(perturb=perturb, no_offset_sampling=bool(no_offset),
+                     force_background=bool(background), no_z_normalize=bool(no_z))
+        r = sdfr.vol_render_opt(ngp=False).rendering
+        r.depth, r.width, r.N_samples = 2, 32, N
+        r.return_sdf, r.return_xyz = True, True
+        for k, v in flags.items():
+            r[k] = v
+        torch.manual_seed(3)
+        ren = sdfr.VolumeFeatureRenderer(r, style_dim=style_dim, out_im_res=res, mode="train")
+        assert isinstance(ren.network, sdfr.renderer.SirenGenerator) and ren.perturb == perturb
+        ext, focal, near, far, _ = sdfr.generate_camera_params(res, "cpu", batch=B)
+        lat = torch.randn(B, style_dim)
+        tr = torch.rand((B, res, res, N) if no_offset else (B, res, res))
+        _, _, sdf, mask, xyz, eik = ren(ext, focal, near, far, styles=lat, return_eikonal=True,
+                                        t_rand=tr)
+        geo = ren.render_geometry(ext, focal, near, far, lat, t_rand=tr,
+                                  want=("sdf", "eikonal", "xyz", "mask"))
+        assert float(geo.eikonal.abs().max()) > 0 and float(geo.mask.abs().max()) > 0, flags
+        assert torch.equal(geo.sdf, sdf.detach()), flags
+        assert torch.equal(geo.eikonal, eik.detach()), flags
+        assert torch.equal(geo.xyz, xyz.detach()), flags
+        assert torch.equal(geo.mask, mask.detach()), flags
