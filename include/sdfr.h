@@ -391,6 +391,96 @@ size_t sdfr_render_ngp_geometry_workspace_bytes(uint32_t B, uint32_t H, uint32_t
 int sdfr_render_ngp_geometry(const sdfr_ngp_weights *w, const sdfr_ngp_geometry_args *a,
                              void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Fused SIREN field query at caller-supplied points (added to ABI 15 without a version
+ * step: additive, nothing existing changes; no reference native op: replaces
+ * SirenGenerator.forward, sdf_model.py:101-139, evaluated op by op on cat([points, dirs])).
+ * The field kernel of sdfr_render_siren_forward with the caller's points in place of the
+ * ray sampler and a per-sample store in place of compositing: the same packed weights
+ * (`prepacked` is sdfr_render_siren_pack's buffer), FiLM vectors, k-step order and
+ * per-sample arithmetic, so a point the render samples gets the render's SDF bit for bit.
+ * The fields mean what sdfr_ngp_query_args' mean: points are NETWORK coordinates, the N
+ * points of a group share one direction, directions are as the network sees them and are
+ * not renormalised.  The SIREN has no grid box: every point runs through the same
+ * arithmetic.
+ * Rate: a wave pair of the kernel takes kPSamples = 4 points of each of 8 groups per
+ * pass, so N = 1 (a direction per point) idles three quarters of its columns, N = 2 half,
+ * N = 3 a quarter; N a multiple of 4 runs at the full rate.  The colour head runs whether
+ * or not rgb is wanted.
+ * Coordinate range: the kernel splits each coordinate into fp16 hi + lo parts without a
+ * scale (the render's arithmetic, kept for the bit-identity above), which is finite below
+ * 65504 and carries a relative error of 2^-22 per coordinate; the accuracy bounds of the
+ * test-suite (against a float64 evaluation, relative to the fp32 module) are checked for
+ * |coordinate| <= 64, the supported range.  The render's samples stay below 1.3.
+ * Workspace: 18 KiB of FiLM vectors per face + the weight-packing region
+ * (sdfr_render_pack_bytes(1)); it does not grow with the point count.
+ * SDFR_EINVAL before any launch for null arguments or required pointers, a null FiLM or
+ * weight pointer, zero sizes, a workspace below sdfr_query_siren_workspace_bytes(B, R, N),
+ * or 2^30 or more padded points B x (R rounded up to 16) x N in one call (the kernel
+ * forms three times a point index in 32 bits; the size function returns 0 for such a
+ * size, and for products that wrap); SDFR_EUNSUPPORTED for depth != 8 or width != 256.
+ * Asynchronous on `stream`; allocates nothing.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfr_siren_query_args {
+    uint32_t B, R, N;        /* faces; direction groups per face; points per group  */
+    const float *points;     /* [B,R,N,3] network coordinates                        */
+    const float *dirs;       /* [B,R,3] direction of each group as the network sees  */
+                             /* it (not normalised again)                            */
+    const float *styles;     /* [B,256] renderer latent                              */
+    float *sdf;              /* [B,R,N]   sigma_linear output           (required)   */
+    float *rgb;              /* [B,R,N,3] sigmoid(rgb_linear) in [0,1], or NULL      */
+    void *workspace; size_t workspace_bytes;
+    const void *prepacked;   /* sdfr_render_siren_pack's buffer, or NULL             */
+} sdfr_siren_query_args;
+size_t sdfr_query_siren_workspace_bytes(uint32_t B, uint32_t R, uint32_t N);
+int sdfr_query_siren_forward(const sdfr_siren_weights *w, const sdfr_siren_query_args *a,
+                             void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Fused SIREN SDF and its exact gradient at caller-supplied points (added to ABI 15
+ * without a version step; replaces autograd through SirenGenerator's SDF trunk, as
+ * get_eikonal_term uses it, sdf_model.py:224-229).  The forward-mode split-fp16 field
+ * kernel of sdfr_query_ngp_grad over pts_linears.0-7 and sigma_linear (no views layer, no
+ * colour): a wave's 32 MFMA columns are 8 points x {value, d/dx, d/dy, d/dz}; layer 0's
+ * value column is the point, its tangent columns the unit vectors; every tangent column
+ * is rescaled by a power of two per layer (FiLM gamma is about 30, so tangents grow by
+ * orders of magnitude per layer) and the exponent is undone exactly at the end.
+ * grad is d sdf / d point in NETWORK coordinates.  There is no grid box and so no
+ * "outside => zero" rule.
+ * The kernel runs on field_r_kernel's k-step loop (32x32x16 MFMA, one slice per k-step),
+ * whose weight layout differs from the render's SIREN packing: the trunk is packed on its
+ * own.  `prepacked` of THIS call is the buffer of sdfr_query_siren_grad_pack
+ * (sdfr_query_siren_grad_pack_bytes() bytes), NOT sdfr_render_siren_pack's; NULL packs
+ * into the workspace on every call.
+ * sdf (optional) is the same SDF as sdfr_query_siren_forward's up to fp32 rounding: the
+ * two kernels accumulate the same products in a different order, and this one scales
+ * layer 0's inputs by a power of two before the fp16 split.  The test-suite bounds the
+ * difference (tests/test_gpu_siren_query.py, profiles/siren_gradient_parity.json).
+ * Coordinate range: any finite fp32 coordinate (layer 0's inputs are pre-scaled); the
+ * accuracy bounds are checked for |coordinate| <= 64.
+ * Workspace: 16 KiB of FiLM vectors per face + the trunk's packing region; it does not
+ * grow with the point count.  SDFR_EINVAL before any launch for null arguments or
+ * required pointers, a null FiLM or weight pointer (sigma_linear and pts_linears; the
+ * colour layers are not read), zero sizes, a workspace below
+ * sdfr_query_siren_grad_workspace_bytes(B, M), or 2^30 or more padded points
+ * B x (M rounded up to 8) in one call (the size function returns 0 for such a size);
+ * SDFR_EUNSUPPORTED for depth != 8 or width != 256.  Asynchronous; allocates nothing.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfr_siren_grad_args {
+    uint32_t B, M;            /* faces; points per face                        */
+    const float *points;      /* [B,M,3] network coordinates                   */
+    const float *styles;      /* [B,256]                                       */
+    float *sdf;               /* [B,M] or NULL                                 */
+    float *grad;              /* [B,M,3] d sdf / d point (network coordinates) */
+    void *workspace; size_t workspace_bytes;
+    const void *prepacked;    /* sdfr_query_siren_grad_pack's buffer, or NULL  */
+} sdfr_siren_grad_args;
+size_t sdfr_query_siren_grad_workspace_bytes(uint32_t B, uint32_t M);
+size_t sdfr_query_siren_grad_pack_bytes(void);
+int sdfr_query_siren_grad_pack(const sdfr_siren_weights *w, void *packed, void *stream);
+int sdfr_query_siren_grad(const sdfr_siren_weights *w, const sdfr_siren_grad_args *a,
+                          void *stream);
+
 #ifdef SDFR_ABLATION
 /* Profiling hooks, exported only by `make ABLATION=1` builds (lib_abl/libsdfr.so,
  * process-global state; never in the product library):

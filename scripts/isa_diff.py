@@ -7,7 +7,10 @@ For every kernel whose demangled name contains one of the substrings (default: t
 render's field / gather kernels) it compares the disassembled body and the kernel
 descriptor's register, scratch and LDS sizes, and prints one line per kernel; with
 --report NAME it also prints those sizes for kernels found only in NEW.so (e.g. a new
-instantiation).  Exit status 1 when a compared kernel differs or is missing.
+instantiation).  --rename OLD=NEW compares the kernel named OLD in OLD.so with the one
+named NEW in NEW.so (full demangled names: a kernel that became a template instantiation
+keeps its code under another symbol).  Exit status 1 when a compared kernel differs or is
+missing.
 
 CPU only: binutils c++filt and llvm-objcopy / llvm-objdump / llvm-readelf of the ROCm LLVM
 ($ROCM_PATH/llvm/bin, default /opt/rocm).
@@ -78,6 +81,12 @@ def kernels(so, tmp):
                 # branch targets are printed with absolute addresses: keep the mnemonic
                 # and operands, drop the "// 0000..." address comments
                 res[cur][0].append(re.sub(r"\s*//.*$", "", line.strip()))
+    # the s_nop fill between a kernel's last s_endpgm and the next symbol's alignment is
+    # not code: it moves with the symbol order (a kernel that becomes a template
+    # instantiation is emitted elsewhere in its section)
+    for body, _ in res.values():
+        while body and body[-1] in ("s_nop 0", "...") and "s_endpgm" in body:
+            body.pop()
     names = run("c++filt", *res.keys()).splitlines() if res else []
     return {d: res[m] for m, d in zip(res.keys(), names)}
 
@@ -88,9 +97,17 @@ def main():
     ap.add_argument("new")
     ap.add_argument("names", nargs="*")
     ap.add_argument("--report", action="append", default=[])
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         ko, kn = kernels(a.old, tmp), kernels(a.new, tmp)
+    renamed = set()
+    for pair in a.rename:
+        old, new = pair.split("=", 1)
+        if old in ko and new in kn and old not in kn:
+            kn[old] = kn.pop(new)
+            renamed.add(old)
+            print(f"RENAMED   {old} -> {new}")
     bad = 0
     for sub in a.names or DEFAULT:
         hits = sorted(k for k in ko if sub in k)
@@ -109,7 +126,7 @@ def main():
                 print(f"          old descriptor: {ko[k][1]}")
             bad += not (same_body and same_meta)
     for sub in a.report:
-        for k in sorted(k for k in kn if sub in k):
+        for k in sorted(k for k in kn if sub in k and k not in ko):
             print(f"NEW       {k}: {len(kn[k][0])} instructions, {kn[k][1]}")
     return 1 if bad else 0
 

@@ -39,6 +39,9 @@ EXPORTS = (
     "sdfr_render_ngp_encode_only", "sdfr_query_ngp_workspace_bytes", "sdfr_query_ngp_forward",
     "sdfr_query_ngp_grad_workspace_bytes", "sdfr_query_ngp_grad",
     "sdfr_render_ngp_geometry_workspace_bytes", "sdfr_render_ngp_geometry",
+    "sdfr_query_siren_workspace_bytes", "sdfr_query_siren_forward",
+    "sdfr_query_siren_grad_workspace_bytes", "sdfr_query_siren_grad_pack_bytes",
+    "sdfr_query_siren_grad_pack", "sdfr_query_siren_grad",
     "sdfr_debug_sin_probe",
     "sdfr_debug_sin_rev_probe", "sdfr_camera_extrinsics",
     "sdfr_render_siren_workspace_bytes", "sdfr_render_siren_forward",
@@ -132,6 +135,16 @@ class NgpGradArgs(ctypes.Structure):
         ("points", _vp), ("styles", _vp), ("sdf", _vp), ("grad", _vp),
         ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("prepacked", _vp),
     ]
+
+
+class SirenQueryArgs(ctypes.Structure):
+    """sdfr_siren_query_args (include/sdfr.h)."""
+    _fields_ = list(NgpQueryArgs._fields_)
+
+
+class SirenGradArgs(ctypes.Structure):
+    """sdfr_siren_grad_args (include/sdfr.h)."""
+    _fields_ = list(NgpGradArgs._fields_)
 
 
 class NgpGeometryArgs(ctypes.Structure):
@@ -250,6 +263,17 @@ def lib():
     L.sdfr_render_siren_pack.argtypes = [ctypes.POINTER(SirenWeights), _vp, _vp]
     L.sdfr_render_siren_forward.argtypes = [ctypes.POINTER(SirenWeights),
                                             ctypes.POINTER(NgpRenderArgs), _vp]
+    L.sdfr_query_siren_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_query_siren_workspace_bytes.argtypes = [_u32, _u32, _u32]
+    L.sdfr_query_siren_forward.argtypes = [ctypes.POINTER(SirenWeights),
+                                           ctypes.POINTER(SirenQueryArgs), _vp]
+    L.sdfr_query_siren_grad_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_query_siren_grad_workspace_bytes.argtypes = [_u32, _u32]
+    L.sdfr_query_siren_grad_pack_bytes.restype = ctypes.c_size_t
+    L.sdfr_query_siren_grad_pack_bytes.argtypes = []
+    L.sdfr_query_siren_grad_pack.argtypes = [ctypes.POINTER(SirenWeights), _vp, _vp]
+    L.sdfr_query_siren_grad.argtypes = [ctypes.POINTER(SirenWeights),
+                                        ctypes.POINTER(SirenGradArgs), _vp]
     L.sdfr_render_fc_workspace_bytes.restype = ctypes.c_size_t
     L.sdfr_render_fc_workspace_bytes.argtypes = [_u32, _u32, _u32, _u32]
     L.sdfr_render_fc_pack.argtypes = [ctypes.POINTER(FcWeights), _vp, _vp]

@@ -133,6 +133,9 @@ struct FcNet {
 struct NgpQueryNet : NgpNet {
     static constexpr bool kQuery = true;
 };
+// (SirenNet's query policy, SirenQueryNet, puts field_p_kernel into the same mode -- the
+// points [B,R,N,3] arrive in XFieldArgs::enc, which the SIREN render leaves unused; it is
+// declared where it is instantiated, csrc/field_query.hip.)
 constexpr int kMaxLayers = 9;
 
 // field_p_kernel's packing (SirenNet): slices = 2 per k-step of 32 input features
@@ -215,8 +218,9 @@ __device__ __forceinline__ void xpin(f2v &x) { asm volatile("" : "+v"(x)); }
 #endif
 constexpr bool kRTailPk = SDFR_RTAILPK != 0;
 
-// SDFR_FIELD_QUERY_TU: csrc/field_query.hip includes this file for the field_r_kernel
-// template alone; the non-template kernels and the host code stay in this unit.
+// SDFR_FIELD_QUERY_TU: csrc/field_query.hip (and field_grad.hip) include this file for the
+// field_r_kernel / field_p_kernel / xprep_kernel templates alone; the non-template kernels
+// and the host code stay in this unit.
 #ifndef SDFR_FIELD_QUERY_TU
 // ----------------------------------------------------------------------------
 // prep 1: per-row power-of-two scales and scaled biases (one wave per row)
@@ -685,6 +689,7 @@ __global__ void __launch_bounds__(kPThreads, 2) field_p_kernel(const XFieldArgs 
     constexpr int NF = Net::kFilmN;
     constexpr int KV = PNet<Net>::kViews;
     constexpr int NL = Net::kLayers;
+    constexpr bool Q = Net::kQuery;                         // point query: no ray, no compositing
     __shared__ f4 ring_lds[kRingSlots * kXSliceF4];           // 64 KB weight ring
     __shared__ uint2 xch_lds[4][2 * 2 * 2 * 2 * 64];        // 32 KB: [pair][slot][block][hi,lo][h][lane]
     __shared__ f4 facc_lds[kPWaves][8 * 4 * 8];             // 32 KB: [wave][tile][g][ray] feature sums
@@ -749,17 +754,28 @@ __global__ void __launch_bounds__(kPThreads, 2) field_p_kernel(const XFieldArgs 
     const uint32_t ray_index = (b * G.H + py) * G.W + px;
 
     Ray ray;
-    make_ray(G.cam + (size_t)b * 12, G.focal[b], G.pix_x[px], G.pix_y[py], G.half_res, ray);
-    const float nr = G.near_[b], fr = G.far_[b];
+    if constexpr (!Q)
+        make_ray(G.cam + (size_t)b * 12, G.focal[b], G.pix_x[px], G.pix_y[py], G.half_res, ray);
+    const float nr = Q ? 0.0f : G.near_[b], fr = Q ? 0.0f : G.far_[b];
     const float span = __fsub_rn(fr, nr);
-    const float dnorm = norm3_torch(ray.d[0], ray.d[1], ray.d[2]);
+    const float dnorm = Q ? 0.0f : norm3_torch(ray.d[0], ray.d[1], ray.d[2]);
     f4 vx[4];                                               // the views layer's extra k-step
     {
-        const float v0 = G.static_viewdirs ? ray.dir[0] : ray.d[0];
-        const float v1 = G.static_viewdirs ? ray.dir[1] : ray.d[1];
-        const float v2 = G.static_viewdirs ? ray.dir[2] : ray.d[2];
-        const float vn = norm3_torch(v0, v1, v2);
-        const float ux = __fdiv_rn(v0, vn), uy = __fdiv_rn(v1, vn), uz = __fdiv_rn(v2, vn);
+        float ux, uy, uz;
+        if constexpr (Q) {
+            // the group's direction as the network sees it (not normalised again):
+            // dirs [B,R,3] in G.cam, ray_index = b R + group (H = 1, W = R)
+            const float *dv = G.cam + (size_t)ray_index * 3;
+            ux = dv[0];
+            uy = dv[1];
+            uz = dv[2];
+        } else {
+            const float v0 = G.static_viewdirs ? ray.dir[0] : ray.d[0];
+            const float v1 = G.static_viewdirs ? ray.dir[1] : ray.d[1];
+            const float v2 = G.static_viewdirs ? ray.dir[2] : ray.d[2];
+            const float vn = norm3_torch(v0, v1, v2);
+            ux = __fdiv_rn(v0, vn), uy = __fdiv_rn(v1, vn), uz = __fdiv_rn(v2, vn);
+        }
         float v[8];
         if constexpr (Net::kSiren) {
 #pragma unroll
@@ -783,8 +799,10 @@ __global__ void __launch_bounds__(kPThreads, 2) field_p_kernel(const XFieldArgs 
     }
     float T = 1.0f, wsum = 0.0f, racc0 = 0.0f, racc1 = 0.0f, racc2 = 0.0f;
     float xacc0 = 0.0f, xacc1 = 0.0f, xacc2 = 0.0f, w_last = 0.0f;
+    if constexpr (!Q) {
 #pragma unroll
-    for (int t = 0; t < 4; ++t) facc[t * 64 + lane] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int t = 0; t < 4; ++t) facc[t * 64 + lane] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
     const size_t tile_sid = (size_t)(tile * G.N) * kTileRays + ray_in_tile;
     float2 en[2][4];
     auto load_inputs = [&](uint32_t p) {
@@ -793,12 +811,20 @@ __global__ void __launch_bounds__(kPThreads, 2) field_p_kernel(const XFieldArgs 
             uint32_t s = kPSamples * p + 2 * c + (colB ? 1u : 0u);
             if (s >= G.N) s = G.N - 1;
             if constexpr (Net::kSiren) {
-                const float z = sample_z(G.sc, nr, fr, ray_index, s);
                 float np_[3];
+                if constexpr (Q) {
+                    // the caller's point (network coordinates): points [B,R,N,3] in a.enc;
+                    // padding groups and samples read a clamped, valid one
+                    const float *pv = a.enc + ((size_t)ray_index * G.N + s) * 3;
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float pp = __fadd_rn(ray.o[k], __fmul_rn(ray.d[k], z));
-                    np_[k] = G.z_normalize ? __fdiv_rn(__fmul_rn(pp, 2.0f), span) : pp;
+                    for (int k = 0; k < 3; ++k) np_[k] = pv[k];
+                } else {
+                    const float z = sample_z(G.sc, nr, fr, ray_index, s);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const float pp = __fadd_rn(ray.o[k], __fmul_rn(ray.d[k], z));
+                        np_[k] = G.z_normalize ? __fdiv_rn(__fmul_rn(pp, 2.0f), span) : pp;
+                    }
                 }
                 const bool g0 = g == 0;
                 en[c][0] = make_float2(g0 ? np_[0] : 0.0f, g0 ? np_[1] : 0.0f);
@@ -916,6 +942,7 @@ __global__ void __launch_bounds__(kPThreads, 2) field_p_kernel(const XFieldArgs 
                     // blocks; exchanged through LDS across this k-step's barrier)
                     sdf_h = __fadd_rn(__fadd_rn(sdfx_lds[pair][0][h][lane], sdfx_lds[pair][1][h][lane]),
                                       sig_b);
+                    if constexpr (Q) return;                 // (this k-step's side only)
                     const uint32_t s = s0 + 2 * h + (colB ? 1u : 0u);
                     const bool s_ok = s < G.N;
                     const uint32_t sc_ = s_ok ? s : G.N - 1;
@@ -942,7 +969,7 @@ __global__ void __launch_bounds__(kPThreads, 2) field_p_kernel(const XFieldArgs 
                         alpha = 1.0f - expf(-sp * dh);
                     }
                     alx_lds[pair][h][lane] = s_ok ? alpha : 0.0f;
-                } else {
+                } else if constexpr (!Q) {
                     // compositing weights of the pass's 4 samples, identically in both
                     // lanes of a ray and both waves of the pair, front to back
                     const float al0 = alx_lds[pair][0][lane], al1 = alx_lds[pair][1][lane];
@@ -1004,7 +1031,7 @@ __global__ void __launch_bounds__(kPThreads, 2) field_p_kernel(const XFieldArgs 
 #pragma unroll
                 for (int o = 0; o < 3; ++o) pcol_lds[pair][3 * c + o][n] = pc[c][o];
         }
-        if (a.features) {
+        if (!Q && a.features) {
             // facc += w0 f0 + w1 f1 + w2 f2 + w3 f3 (in that order) by the lane of the
             // ray's samples 0 and 2 (block 0 / 1, n < 8)
 #pragma unroll
@@ -1038,6 +1065,22 @@ __global__ void __launch_bounds__(kPThreads, 2) field_p_kernel(const XFieldArgs 
                 q[c][0] = sigmoidf_(__fadd_rn(__fadd_rn(pcol_lds[pair][3 * c][n], pc[c][0]), rgb_b0));
                 q[c][1] = sigmoidf_(__fadd_rn(__fadd_rn(pcol_lds[pair][3 * c + 1][n], pc[c][1]), rgb_b1));
                 q[c][2] = sigmoidf_(__fadd_rn(__fadd_rn(pcol_lds[pair][3 * c + 2][n], pc[c][2]), rgb_b2));
+            }
+            if constexpr (Q) {
+                // the sample's own colour [B,R,N,3] (the render composites these values)
+                if (a.rgb && ray_ok && g == 0) {
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const uint32_t s = s0 + 2 * c + (colB ? 1u : 0u);
+                        if (s < G.N) {
+                            float *o = a.rgb + ((size_t)ray_index * G.N + s) * 3;
+                            o[0] = q[c][0];
+                            o[1] = q[c][1];
+                            o[2] = q[c][2];
+                        }
+                    }
+                }
+                continue;
             }
             float racc[3] = {racc0, racc1, racc2};
 #pragma unroll
@@ -1074,6 +1117,7 @@ __global__ void __launch_bounds__(kPThreads, 2) field_p_kernel(const XFieldArgs 
     }
     // the ring runs ahead across passes: no LDS-DMA may land after the workgroup ends
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (Q) return;                                // per-sample stores only
     if (!ray_ok || colB) return;
     if (a.nseg > 1) {
         const size_t Rr = (size_t)G.total_tiles * kTileRays;
@@ -2310,6 +2354,62 @@ static int siren_validate(const sdfr_siren_weights *w, const sdfr_ngp_render_arg
     return SDFR_OK;
 }
 
+// Point calls (query, gradient).  The kernels form 3 x (point index) in 32 bits, so a call
+// takes fewer than 2^30 padded points.  The query's padded count is
+// S = B x (R rounded up to 16) x N, formed in steps that cannot wrap 64 bits (0: too many);
+// the gradient's is P = B x (M rounded up to 8) < 2^64.
+constexpr uint64_t kSirenMaxPoints = 1ull << 30;
+static uint64_t siren_query_padded(uint32_t B, uint32_t R, uint32_t N) {
+    const uint64_t Rp = ((uint64_t)R + kTileRays - 1) / kTileRays * kTileRays;
+    if (Rp >= kSirenMaxPoints || (uint64_t)B * Rp >= kSirenMaxPoints) return 0;
+    const uint64_t S = (uint64_t)B * Rp * N;
+    return S >= kSirenMaxPoints ? 0 : S;
+}
+
+// gradient: film [B][8][2][256] | the trunk's packing (siren_grad_pack_bytes)
+static size_t siren_grad_ws_layout(uint32_t B, uint32_t M, uint64_t *P_out, size_t *o_x) {
+    const uint64_t Mp = ((uint64_t)M + kGradPts - 1) / kGradPts * kGradPts;
+    const uint64_t P = (uint64_t)B * Mp;
+    if (P_out) *P_out = P;
+    if (P == 0 || P >= kSirenMaxPoints) return 0;
+    const size_t off = align256x((size_t)B * 8 * 2 * kW * sizeof(float));
+    if (o_x) *o_x = off;
+    return off + align256x(siren_grad_pack_bytes());
+}
+
+static int siren_check_weights(const sdfr_siren_weights *w, const char *who, bool colour) {
+    auto err = [&](int code, const char *what) { return fail(code, std::string(who) + ": " + what); };
+    if (w->depth != 8 || w->width != 256)
+        return err(SDFR_EUNSUPPORTED, "fused path needs depth 8, width 256");
+    for (int l = 0; l < 8; ++l)
+        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
+            !w->pts_bb[l])
+            return err(SDFR_EINVAL, "FiLM weight pointer is null");
+    if (!w->sigma_w || !w->sigma_b) return err(SDFR_EINVAL, "weight pointer is null");
+    if (colour) {
+        const void *need[] = {w->views_w, w->views_b, w->views_gw, w->views_gb,
+                              w->views_bw, w->views_bb, w->rgb_w, w->rgb_b};
+        for (const void *p : need)
+            if (!p) return err(SDFR_EINVAL, "weight pointer is null");
+    }
+    return SDFR_OK;
+}
+
+int launch_xscale(const float *const *w, const float *const *b, const uint32_t *K, int layers,
+                  float *su, float *bias_s, hipStream_t st) {
+    XScaleArgs sa{};
+    for (int l = 0; l < layers; ++l) {
+        sa.w[l] = w[l];
+        sa.b[l] = b[l];
+        sa.K[l] = K[l];
+    }
+    sa.su = su;
+    sa.bias_s = bias_s;
+    sa.raw_bias0 = 0;
+    hipLaunchKernelGGL(xscale_kernel, dim3(layers, kW / 4), dim3(256), 0, st, sa);
+    return check_launch("render: xscale");
+}
+
 // ----------------------------------------------------------------------------
 // FCGenerator entry points
 // ----------------------------------------------------------------------------
@@ -2449,6 +2549,89 @@ int sdfr_render_siren_forward(const sdfr_siren_weights *w, const sdfr_ngp_render
     if ((rc = launch_xfield<SirenNet>(P, a, g, nullptr, ws + o_x, film, st))) return rc;
     record_event(a->stage_events[3], st);
     return SDFR_OK;
+}
+
+// ----------------------------------------------------------------------------
+// SIREN field query and SDF gradient at caller points (kernels: field_query.hip,
+// field_grad.hip)
+// ----------------------------------------------------------------------------
+size_t sdfr_query_siren_workspace_bytes(uint32_t B, uint32_t R, uint32_t N) {
+    return siren_query_padded(B, R, N) ? siren_ws_layout(B, nullptr) : 0;
+}
+
+int sdfr_query_siren_forward(const sdfr_siren_weights *w, const sdfr_siren_query_args *a,
+                             void *stream) {
+    if (!w || !a) return fail(SDFR_EINVAL, "query_siren: null args");
+    if (a->B == 0 || a->R == 0 || a->N == 0)
+        return fail(SDFR_EINVAL, "query_siren: empty batch / group / point count");
+    if (!a->points || !a->dirs || !a->styles || !a->sdf || !a->workspace)
+        return fail(SDFR_EINVAL, "query_siren: required pointer is null");
+    int rc = siren_check_weights(w, "query_siren", true);
+    if (rc) return rc;
+    const uint64_t S = siren_query_padded(a->B, a->R, a->N);
+    if (S == 0)
+        return fail(SDFR_EINVAL, "query_siren: too many samples per call (split the points)");
+    size_t o_x;
+    if (a->workspace_bytes < siren_ws_layout(a->B, &o_x))
+        return fail(SDFR_EINVAL, "query_siren: workspace too small");
+
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(a->workspace);
+    float *film = reinterpret_cast<float *>(ws);
+    GeomArgs g{};
+    g.B = a->B;
+    g.H = 1;
+    g.W = a->R;
+    g.N = a->N;
+    g.tiles_per_face = (a->R + kTileRays - 1) / kTileRays;
+    g.total_tiles = a->B * g.tiles_per_face;
+    g.S_total = (uint32_t)S;
+    g.cam = a->dirs;
+    if ((rc = launch_xprep<SirenNet>(siren_ptrs(w), a->B, a->styles, a->prepacked, ws + o_x, film,
+                                     st)))
+        return rc;
+    const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
+    return launch_qfield_siren(w, g, a->points, xws, film, a->sdf, a->rgb, st);
+}
+
+size_t sdfr_query_siren_grad_pack_bytes(void) { return siren_grad_pack_bytes(); }
+
+int sdfr_query_siren_grad_pack(const sdfr_siren_weights *w, void *packed, void *stream) {
+    if (!w || !packed) return fail(SDFR_EINVAL, "query_siren_grad_pack: null pointer");
+    int rc = siren_check_weights(w, "query_siren_grad_pack", false);
+    if (rc) return rc;
+    return launch_gprep_siren(w, 0, nullptr, reinterpret_cast<char *>(packed), nullptr, true,
+                              (hipStream_t)stream);
+}
+
+size_t sdfr_query_siren_grad_workspace_bytes(uint32_t B, uint32_t M) {
+    return siren_grad_ws_layout(B, M, nullptr, nullptr);
+}
+
+int sdfr_query_siren_grad(const sdfr_siren_weights *w, const sdfr_siren_grad_args *a,
+                          void *stream) {
+    if (!w || !a) return fail(SDFR_EINVAL, "query_siren_grad: null args");
+    if (a->B == 0 || a->M == 0)
+        return fail(SDFR_EINVAL, "query_siren_grad: empty batch / point count");
+    if (!a->points || !a->styles || !a->grad || !a->workspace)
+        return fail(SDFR_EINVAL, "query_siren_grad: required pointer is null");
+    int rc = siren_check_weights(w, "query_siren_grad", false);
+    if (rc) return rc;
+    uint64_t P;
+    size_t o_x = 0;
+    const size_t need_ws = siren_grad_ws_layout(a->B, a->M, &P, &o_x);
+    if (P >= kSirenMaxPoints)
+        return fail(SDFR_EINVAL, "query_siren_grad: too many points per call (split the points)");
+    if (a->workspace_bytes < need_ws)
+        return fail(SDFR_EINVAL, "query_siren_grad: workspace too small");
+
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(a->workspace);
+    float *film = reinterpret_cast<float *>(ws);
+    char *xws = a->prepacked ? const_cast<char *>(reinterpret_cast<const char *>(a->prepacked))
+                             : ws + o_x;
+    if ((rc = launch_gprep_siren(w, a->B, a->styles, xws, film, !a->prepacked, st))) return rc;
+    return launch_gfield_siren(w, xws, film, a->points, a->sdf, a->grad, a->B, a->M, st);
 }
 
 }  // extern "C"

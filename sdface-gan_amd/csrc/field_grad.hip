@@ -7,6 +7,10 @@
 //                            pts_linears.1-2, sigma_linear) on split-fp16 MFMA: the value and
 //                            its three tangents are four MFMA columns of one GEMM stream
 //
+// field_g_kernel is a template over the trunk (NgpGradNet here; SirenGradNet, the SIREN's
+// eight FiLM layers with no gather, at the end of this file).  What follows describes the
+// ngp instantiation; the SIREN section says what differs.
+//
 // Gather layout (gd): [B Mp][4 kinds][32] fp32, Mp = M rounded up to 8 (one wave pass);
 // kind 0 holds the features (feature 2 level + c), kind 1 + k their derivatives d/du_k.
 // 512 B per padded point; padding points and points outside [0,1]^3 hold zeros.  One
@@ -129,17 +133,23 @@ struct NgpGradNet {
     static constexpr bool kFieldR = true;
     static constexpr int kFilmN = 3;             // pts_linears.0-2
     static constexpr uint32_t kSlices = 2 + 16 * 2;
+    static constexpr bool kGather = true;        // layer-0 columns from the gather's gd
+    static constexpr uint32_t kFilmStride = kFilm;   // FiLM sets per face in `film`
 };
 
+static_assert(RNet<NgpGradNet>::kSteps == 34 && NgpGradNet::kSlices == 34, "ngp trunk k-steps");
+static_assert(kGradPts * 4 == 32 && kGGroup == 32, "8 points x 4 kinds per wave, 32 per pass");
+
 struct GFieldArgs {
-    const float *gd;               // [B Mp][4][32]
-    const f4 *packed;              // NgpNet's packed weights (first 34 slices read)
-    const float *film;             // [B][kFilm = 4][2][256] (xprep_kernel<NgpNet>)
+    const float *gd;               // ngp: [B Mp][4][32]; siren: the points [B,M,3]
+    const f4 *packed;              // NgpNet's packed weights (first 34 slices read) /
+                                   // SirenGradNet's (113 slices)
+    const float *film;             // [B][kFilmStride][2][256] (xprep_kernel)
     const float *sigma_w, *sigma_b;
     float *sdf;                    // [B,M] or null
     float *grad;                   // [B,M,3]
     uint32_t M, Mp, wg_per_face;
-    float bound;
+    float bound;                   // ngp only
 };
 
 __device__ __forceinline__ float quad_bcast0(float v) {   // lane n <- lane n & ~3
@@ -172,12 +182,13 @@ __device__ __forceinline__ float g_act1(float zz, float g, float b, float w, boo
     return v;
 }
 
+template <class Net>
 __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs a) {
-    using Net = NgpGradNet;
     constexpr int NF = Net::kFilmN;
     constexpr int KL0 = Net::kL0;
+    constexpr int KH = Net::kHidden;                        // the last FiLM layer (sigma head)
     constexpr int NS = RNet<Net>::kSteps;
-    static_assert(NS == 34 && (NS & 1) == 0, "the SDF trunk's k-steps");
+    static_assert(NS == KL0 + 16 * KH && NS == (int)Net::kSlices, "the SDF trunk's k-steps");
     __shared__ f4 ring_lds[4 * kRSliceF4];                  // 64 KB weight ring
     __shared__ float film_lds[NF * 2 * kW];                 // the workgroup's face
     __shared__ float cst[kW];                               // sigma_w
@@ -188,7 +199,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
     const bool tangent = kind != 0u;
     const uint32_t b = blockIdx.x / a.wg_per_face, wg = blockIdx.x % a.wg_per_face;
     {
-        const f4 *src = reinterpret_cast<const f4 *>(a.film + (size_t)b * kFilm * 2 * kW);
+        const f4 *src = reinterpret_cast<const f4 *>(a.film + (size_t)b * Net::kFilmStride * 2 * kW);
         f4 *dst = reinterpret_cast<f4 *>(film_lds);
         for (uint32_t i = tid; i < NF * 2 * kW / 4; i += kRThreads) dst[i] = src[i];
     }
@@ -219,23 +230,34 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
     auto load_inputs = [&](uint32_t p) {
         uint32_t m = point_of(p);
         if (m >= a.M) m = a.M - 1;
-        const float *src = a.gd + ((b * a.Mp + m) * 4u + kind) * kFeatIn + 8u * h;
+        if constexpr (Net::kGather) {
+            const float *src = a.gd + ((b * a.Mp + m) * 4u + kind) * kFeatIn + 8u * h;
 #pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            ld[2 * st] = *reinterpret_cast<const f4 *>(src + 16 * st);
-            ld[2 * st + 1] = *reinterpret_cast<const f4 *>(src + 16 * st + 4);
+            for (int st = 0; st < 2; ++st) {
+                ld[2 * st] = *reinterpret_cast<const f4 *>(src + 16 * st);
+                ld[2 * st + 1] = *reinterpret_cast<const f4 *>(src + 16 * st + 4);
+            }
+        } else {
+            // the point itself (value column) or the unit vector e_(kind - 1) (tangent
+            // columns) in K rows 0-2 of lane half 0; every other row of the k-step is zero
+            const float *src = a.gd + ((size_t)b * a.M + m) * 3;
+            const float px = src[0], py = src[1], pz = src[2];
+            const bool h0 = h == 0u;
+            ld[0] = f4{h0 ? (kind == 0u ? px : (kind == 1u ? 1.0f : 0.0f)) : 0.0f,
+                       h0 ? (kind == 0u ? py : (kind == 2u ? 1.0f : 0.0f)) : 0.0f,
+                       h0 ? (kind == 0u ? pz : (kind == 3u ? 1.0f : 0.0f)) : 0.0f, 0.0f};
         }
     };
     load_inputs(wg);
 
     uint32_t it = 0;
     for (uint32_t p = wg; p < npass; p += a.wg_per_face, ++it) {
-        R.ubase = __builtin_amdgcn_readfirstlane((it * (uint32_t)(NS / 2)) & 1u);
+        R.ubase = __builtin_amdgcn_readfirstlane((it * (uint32_t)((NS + 1) / 2)) & 1u);
         r_na(R, r_slot<Net>(R, 0));
         f16v X[8], Y[8];
         f4 bf[2], bn[2], E[KL0][2];
         int es = 0;                                         // the column's layer-0 input scale
-        {
+        if constexpr (Net::kGather) {
             float v[16];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -260,6 +282,19 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
             }
             split8(u0, E[0][0], E[0][1]);
             split8(u1, E[1][0], E[1][1]);
+        } else {
+            // the column's 3 inputs (lane half 0; half 1 holds zeros) -> 2^es into [0.5, 1):
+            // the hi / lo split is then fp32-accurate at any coordinate magnitude
+            float v[8] = {ld[0][0], ld[0][1], ld[0][2], 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));
+            m = fmaxf(m, __shfl_xor(m, 32));
+            if (m > 0.0f && m < 3.0e38f) {
+                const int ex = __builtin_amdgcn_frexp_expf(m);
+                es = ex < -100 ? 100 : -ex;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) v[j] = __builtin_ldexpf(v[j], es);
+            }
+            split8(v, E[0][0], E[0][1]);
         }
         int ts = es;                                        // tangent: cumulative scale exponent
         float sdfp = 0.0f;
@@ -275,7 +310,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
             as.gm1 = *reinterpret_cast<const f4 *>(fg(l) + r0 + 8);
             as.bt0 = *reinterpret_cast<const f4 *>(fb(l) + r0);
             as.bt1 = *reinterpret_cast<const f4 *>(fb(l) + r0 + 8);
-            if constexpr (l == 2) {
+            if constexpr (l == KH) {
                 as.w0 = *reinterpret_cast<const f4 *>(sig_w + r0);
                 as.w1 = *reinterpret_cast<const f4 *>(sig_w + r0 + 8);
             }
@@ -285,8 +320,9 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
             constexpr int l = decltype(L)::value;
             const float g = j < 4 ? as.gm0[j & 3] : as.gm1[j & 3];
             const float bb = j < 4 ? as.bt0[j & 3] : as.bt1[j & 3];
-            const float w = l == 2 ? (j < 4 ? as.w0[j & 3] : as.w1[j & 3]) : 0.0f;
-            as.v[j] = g_act1<l>(o[q >> 1][8 * (q & 1) + j], g, bb, w, tangent, es, ex, sdfp);
+            const float w = l == KH ? (j < 4 ? as.w0[j & 3] : as.w1[j & 3]) : 0.0f;
+            constexpr int MODE = l == 0 ? 0 : (l == KH ? 2 : 1);
+            as.v[j] = g_act1<MODE>(o[q >> 1][8 * (q & 1) + j], g, bb, w, tangent, es, ex, sdfp);
         };
         // activation of chunk q into bn spread over a k-step's groups: film vectors read
         // beside group 0, one register beside each of groups 1-5, two beside group 6, the
@@ -329,9 +365,7 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
             return tangent ? ex : 0;
         };
         constexpr std::integral_constant<int, 0> L0{};
-        constexpr std::integral_constant<int, 1> L1{};
-        constexpr std::integral_constant<int, 2> L2{};
-        // layer 0: K = 32, 2 k-steps
+        // layer 0: K = 32 (ngp, 2 k-steps) or 3 (siren, 1)
         sfor<0, KL0>([&](auto J) {
             constexpr int j = decltype(J)::value;
             bf[0] = E[j][0];
@@ -342,37 +376,43 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
         ts -= ex;
         act_now(L0, X, 0, ex);
         split8(as.v, bn[0], bn[1]);
-        // dense layer 1: X -> Y, activating layer 0's chunks one k-step ahead
-        sfor<0, 16>([&](auto J) {
-            constexpr int j = decltype(J)::value;
-            bf[0] = bn[0];
-            bf[1] = bn[1];
-            rstep<Net, KL0 + j, j == 0>(R, Y, bf, [&](auto GI) {
-                if constexpr (j < 15) act_side(L0, X, j + 1, GI, ex);
+        // dense layers 1 .. KH (in -> out alternate X / Y), each activating the previous
+        // layer's chunks one k-step ahead; the next pass's inputs are loaded under the last
+        // layer's last k-steps
+        auto dense = [&](auto L, f16v (&in)[8], f16v (&out)[8]) {
+            constexpr int l = decltype(L)::value;
+            constexpr std::integral_constant<int, l - 1> LP{};
+            const bool more = p + a.wg_per_face < npass;    // (read by the last layer only)
+            sfor<0, 16>([&](auto J) {
+                constexpr int j = decltype(J)::value;
+                bf[0] = bn[0];
+                bf[1] = bn[1];
+                if constexpr (l == KH && j == 12) {
+                    if (more) load_inputs(p + a.wg_per_face);
+                }
+                rstep<Net, KL0 + 16 * (l - 1) + j, j == 0>(R, out, bf, [&](auto GI) {
+                    if constexpr (j < 15) act_side(LP, in, j + 1, GI, ex);
+                });
             });
-        });
-        ex = col_scale(L1, Y);
-        ts -= ex;
-        act_now(L1, Y, 0, ex);
-        split8(as.v, bn[0], bn[1]);
-        // dense layer 2: Y -> X; the next pass's inputs are loaded under its last k-steps
-        const bool more = p + a.wg_per_face < npass;
-        sfor<0, 16>([&](auto J) {
-            constexpr int j = decltype(J)::value;
-            bf[0] = bn[0];
-            bf[1] = bn[1];
-            if constexpr (j == 12) {
-                if (more) load_inputs(p + a.wg_per_face);
+            if constexpr (l < KH) {
+                ex = col_scale(L, out);
+                ts -= ex;
+                act_now(L, out, 0, ex);
+                split8(as.v, bn[0], bn[1]);
             }
-            rstep<Net, KL0 + 16 + j, j == 0>(R, X, bf, [&](auto GI) {
-                if constexpr (j < 15) act_side(L1, Y, j + 1, GI, ex);
-            });
+        };
+        sfor<1, KH + 1>([&](auto L) {
+            constexpr int l = decltype(L)::value;
+            if constexpr (l & 1) dense(L, X, Y);
+            else dense(L, Y, X);
         });
         // last FiLM layer and sigma_linear: the value column's dot product in
         // field_r_kernel's order (chunks 0..15, registers 0..7), the tangents' likewise
         // without the bias
+        f16v (&last)[8] = (KH & 1) ? Y : X;
+        constexpr std::integral_constant<int, KH> LH{};
 #pragma unroll
-        for (int q = 0; q < 16; ++q) act_now(L2, X, q, 0);
+        for (int q = 0; q < 16; ++q) act_now(LH, last, q, 0);
         const float tot = __fadd_rn(sdfp, __shfl_xor(sdfp, 32));
         const uint32_t m = point_of(p);
         if (h == 0 && m < a.M) {
@@ -380,9 +420,11 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
             if (!tangent) {
                 if (a.sdf) a.sdf[o] = __fadd_rn(tot, sig_b);
             } else {
-                // d sdf / d u_k, then / (2 bound): the derivative of u = (p + bound) / (2 bound)
+                // ngp: d sdf / d u_k, then / (2 bound): the derivative of
+                // u = (p + bound) / (2 bound); siren: the columns are d / d point already
+                const float gk = __builtin_ldexpf(tot, -ts);
                 a.grad[o * 3 + (kind - 1u)] =
-                    __fdiv_rn(__builtin_ldexpf(tot, -ts), __fmul_rn(2.0f, a.bound));
+                    Net::kGather ? __fdiv_rn(gk, __fmul_rn(2.0f, a.bound)) : gk;
             }
         }
     }
@@ -430,8 +472,119 @@ int launch_gfield_ngp(const sdfr_ngp_weights *w, const char *xws, const float *f
     const uint32_t npass = (Mp + kGGroup - 1) / kGGroup;
     const uint32_t want = (1024u + B - 1) / B;
     f.wg_per_face = npass < want ? npass : want;
-    hipLaunchKernelGGL(field_g_kernel, dim3(B * f.wg_per_face), dim3(kRThreads), 0, st, f);
+    hipLaunchKernelGGL(field_g_kernel<NgpGradNet>, dim3(B * f.wg_per_face), dim3(kRThreads), 0, st,
+                       f);
     return check_launch("query_ngp_grad: field (f16x3)");
+}
+
+// ----------------------------------------------------------------------------
+// SIREN: the SDF and its gradient at caller points (sdfr_query_siren_grad, entry points
+// in field_f16x3.hip)
+//
+//   xprep_kernel<SirenGradNet>    FiLM vectors of the faces' styles and (once per weight
+//                                 version: sdfr_query_siren_grad_pack) the trunk's weights
+//                                 in field_r_kernel's packing
+//   field_g_kernel<SirenGradNet>  the forward-mode kernel over pts_linears.0-7 and
+//                                 sigma_linear
+//
+// There is no gather: layer 0's value column is the point (x, y, z, 0, ...) and tangent
+// column k the unit vector e_k, both scaled by a power of two into [0.5, 1) before the
+// hi / lo split as the ngp columns are.  FiLM gamma is about 30, so a tangent grows by
+// orders of magnitude per layer: the per-layer power-of-two rescale, which the ngp
+// trunk's two layers barely need, is what keeps the seven dense layers' tangent columns
+// inside fp16's range.  Instantiated beside the ngp kernel: this unit's ngp kernels come
+// out of the compiler unchanged with it (profiles/siren_query_isa.txt).
+// ----------------------------------------------------------------------------
+// The SDF trunk of SirenNet (pts_linears.0-7, sigma_linear): layer 0 (one k-step on the
+// point itself) and seven dense layers, in field_r_kernel's packing -- one slice per
+// k-step of 16 K, K permuted by rperm_k.  The render's SIREN packing is field_p_kernel's
+// (half-slices per k-step of 32 K), so this trunk is packed on its own
+// (sdfr_query_siren_grad_pack: xprep_kernel<SirenGradNet>, r_pack).  kLayers counts a
+// views layer of zero k-steps so that rslice_base / rperm_k index the dense layers as they
+// do for the render policies; there are eight weight matrices and eight FiLM sets.
+struct SirenGradNet {
+    static constexpr bool kSiren = true;
+    static constexpr bool kGrid = false;
+    static constexpr bool kPosEnc = false;
+    static constexpr bool kSinAct = true;
+    static constexpr int kL0 = 1;
+    static constexpr int kHidden = 7;
+    static constexpr int kViewSteps = 0;
+    static constexpr bool kFieldR = true;
+    static constexpr bool kQuery = false;
+    static constexpr bool kCompose = false;
+    static constexpr int kLayers = 9;            // pts_linears.0-7 (+ the absent views layer)
+    static constexpr int kMats = 8;              // weight matrices, row scales, FiLM sets
+    static constexpr int kFilmN = 8;
+    static constexpr uint32_t kSlices = 1 + 16 * 7;
+    static constexpr bool kGather = false;       // layer-0 columns: the point and unit vectors
+    static constexpr uint32_t kFilmStride = 8;
+    __host__ __device__ static constexpr uint32_t K(int l) { return l == 0 ? 3u : kW; }
+    __host__ __device__ static constexpr int film_layer(int f) { return f; }
+};
+static_assert(RNet<SirenGradNet>::kSteps == 113 && SirenGradNet::kSlices == 113 &&
+                  rslice_base<SirenGradNet>(7) == 97,
+              "siren trunk: one slice per k-step, dense layer l at 1 + 16 (l - 1)");
+
+// ----------------------------------------------------------------------------
+// SIREN host side
+// ----------------------------------------------------------------------------
+size_t siren_grad_pack_bytes() {
+    return (size_t)SirenGradNet::kSlices * kRSliceF4 * sizeof(f4) +
+           2 * (size_t)SirenGradNet::kMats * kW * sizeof(float);
+}
+
+int launch_gprep_siren(const sdfr_siren_weights *w, uint32_t B, const float *styles, char *xws,
+                       float *film, bool pack, hipStream_t st) {
+    using Net = SirenGradNet;
+    float *su = reinterpret_cast<float *>(xws + (size_t)Net::kSlices * kRSliceF4 * sizeof(f4));
+    if (pack) {
+        uint32_t K[Net::kMats];
+        for (int l = 0; l < Net::kMats; ++l) K[l] = Net::K(l);
+        int rc = launch_xscale(w->pts_w, w->pts_b, K, Net::kMats, su, su + Net::kMats * kW, st);
+        if (rc) return rc;
+    }
+    XPrepArgs p{};
+    p.styles = styles;
+    for (int l = 0; l < Net::kMats; ++l) {
+        p.gw[l] = w->pts_gw[l];
+        p.gb[l] = w->pts_gb[l];
+        p.bw[l] = w->pts_bw[l];
+        p.bb[l] = w->pts_bb[l];
+        p.w[l] = w->pts_w[l];
+        p.lb[l] = w->pts_b[l];
+    }
+    p.su = su;
+    p.film = film;
+    p.packed = reinterpret_cast<f4 *>(xws);
+    p.B = film ? B : 0;
+    const uint32_t nfilm = p.B * Net::kFilmN * 2 * kW / 4;
+    const uint32_t blocks = nfilm + (pack ? (Net::kSlices * 512 + 255) / 256 : 0);
+    if (blocks == 0) return SDFR_OK;
+    hipLaunchKernelGGL(xprep_kernel<Net>, dim3(blocks), dim3(256), 0, st, p);
+    return check_launch("query_siren_grad: xprep");
+}
+
+int launch_gfield_siren(const sdfr_siren_weights *w, const char *xws, const float *film,
+                        const float *points, float *sdf, float *grad, uint32_t B, uint32_t M,
+                        hipStream_t st) {
+    GFieldArgs f{};
+    f.gd = points;
+    f.packed = reinterpret_cast<const f4 *>(xws);
+    f.film = film;
+    f.sigma_w = w->sigma_w;
+    f.sigma_b = w->sigma_b;
+    f.sdf = sdf;
+    f.grad = grad;
+    f.M = M;
+    f.Mp = (M + kGradPts - 1) / kGradPts * kGradPts;
+    // as launch_gfield_ngp: a face's passes round robin over about four workgroups per CU
+    const uint32_t npass = (f.Mp + kGGroup - 1) / kGGroup;
+    const uint32_t want = (1024u + B - 1) / B;
+    f.wg_per_face = npass < want ? npass : want;
+    hipLaunchKernelGGL(field_g_kernel<SirenGradNet>, dim3(B * f.wg_per_face), dim3(kRThreads), 0,
+                       st, f);
+    return check_launch("query_siren_grad: field (f16x3)");
 }
 
 }  // namespace sdfr

@@ -13,6 +13,12 @@
 // context, so a query instantiation beside the render's would move the render kernels'
 // code.  This unit includes that source for the templates alone (SDFR_FIELD_QUERY_TU
 // leaves out its non-template kernels and host code) and is built with the same flags.
+//
+// The SIREN query (sdfr_query_siren_forward, entry point in field_f16x3.hip) is
+// field_p_kernel<SirenQueryNet>, at the end of this file: the render's wave-pair kernel
+// with the point and the group's direction read from memory.  It has no gather and no
+// staging kernel.  field_r_kernel<NgpQueryNet> comes out of the compiler unchanged beside
+// it (profiles/siren_query_isa.txt).
 #define SDFR_FIELD_QUERY_TU 1
 #include "field_f16x3.hip"
 
@@ -87,6 +93,44 @@ int launch_qfield_ngp(const sdfr_ngp_weights *w, const GeomArgs &g, const float 
     const uint32_t blocks = g.B * ((g.tiles_per_face + kRTiles - 1) / kRTiles);
     hipLaunchKernelGGL((field_r_kernel<Net>), dim3(blocks), dim3(kRThreads), 0, st, f);
     return check_launch("query_ngp: field (f16x3)");
+}
+
+// SirenNet in query mode (sdfr_query_siren_forward): field_p_kernel at the caller's points,
+// as NgpQueryNet is field_r_kernel's.  The SIREN has no gather stage, so there is no
+// staging kernel either: a lane reads its point (12 bytes of points [B,R,N,3], passed in
+// XFieldArgs::enc) where the render forms its sample from the ray -- 12 bytes per 1.1
+// MFLOP of MLP.  Same packed weights (sdfr_render_siren_pack), FiLM vectors and k-step
+// order as the render.
+struct SirenQueryNet : SirenNet {
+    static constexpr bool kQuery = true;
+};
+static_assert(PNet<SirenQueryNet>::kSteps == PNet<SirenNet>::kSteps &&
+                  SirenQueryNet::kSlices == SirenNet::kSlices && kPTiles * kTileRays == 32 &&
+                  kPSamples == 4,
+              "the query runs the render's k-steps on the render's packing");
+
+// g: B faces, H = 1, W = R, N points per group, cam = dirs [B,R,3].
+int launch_qfield_siren(const sdfr_siren_weights *w, const GeomArgs &g, const float *points,
+                        const char *xws, const float *film, float *sdf, float *rgb,
+                        hipStream_t st) {
+    using Net = SirenQueryNet;
+    XFieldArgs f{};
+    f.g = g;
+    f.enc = points;
+    f.packed = reinterpret_cast<const f4 *>(xws);
+    f.su = reinterpret_cast<const float *>(xws + (size_t)Net::kSlices * kXSliceF4 * sizeof(f4));
+    f.bias_s = f.su + Net::kLayers * kW;
+    f.film = film;
+    f.sigma_w = w->sigma_w;
+    f.sigma_b = w->sigma_b;
+    f.rgb_w = w->rgb_w;
+    f.rgb_b = w->rgb_b;
+    f.sdf = sdf;
+    f.rgb = rgb;
+    f.nseg = 1;
+    const uint32_t blocks = g.B * ((g.tiles_per_face + kPTiles - 1) / kPTiles);
+    hipLaunchKernelGGL((field_p_kernel<Net>), dim3(blocks), dim3(kPThreads), 0, st, f);
+    return check_launch("query_siren: field (f16x3)");
 }
 
 }  // namespace sdfr

@@ -156,6 +156,25 @@ int launch_grad_gather(const sdfr_ngp_weights *w, const float *points, float *gd
 int launch_gfield_ngp(const sdfr_ngp_weights *w, const char *xws, const float *film,
                       const float *gd, float *sdf, float *grad, uint32_t B, uint32_t M,
                       uint32_t Mp, hipStream_t st);
+// SIREN field query (field_query.hip): field_p_kernel in query mode on the render's packed
+// weights (g as for launch_qfield_ngp; points [B,R,N,3] network coordinates).
+int launch_qfield_siren(const sdfr_siren_weights *w, const GeomArgs &g, const float *points,
+                        const char *xws, const float *film, float *sdf, float *rgb,
+                        hipStream_t st);
+// SIREN SDF and gradient (field_grad.hip): the SDF trunk in field_r_kernel's packing
+// (siren_grad_pack_bytes(): packed slices | su [8][256] | bias_s [8][256]).
+// launch_gprep_siren: FiLM vectors film [B][8][2][256] and, with `pack`, the row scales
+// and the packing into xws (B = 0, film null: packing only); launch_gfield_siren: the
+// forward-mode field kernel on points [B,M,3].  launch_xscale (field_f16x3.hip): the
+// per-row power-of-two scales of `layers` weight matrices [256][K[l]].
+size_t siren_grad_pack_bytes();
+int launch_xscale(const float *const *w, const float *const *b, const uint32_t *K, int layers,
+                  float *su, float *bias_s, hipStream_t st);
+int launch_gprep_siren(const sdfr_siren_weights *w, uint32_t B, const float *styles, char *xws,
+                       float *film, bool pack, hipStream_t st);
+int launch_gfield_siren(const sdfr_siren_weights *w, const char *xws, const float *film,
+                        const float *points, float *sdf, float *grad, uint32_t B, uint32_t M,
+                        hipStream_t st);
 // Geometry render (geometry.hip): the cameras' samples in plain [B,H,W,N] order as the
 // gradient gather's points (pnet [S,3], zd [S] = (z, dist), S = B H W N), and the
 // compositing of the gradient call's sdf [S] / gnet [S,3] into per-sample eikonal [S,3]

@@ -720,33 +720,43 @@ class VolumeFeatureRenderer(nn.Module):
                    name)
         return rgb, features, sdf, mask, xyz, None
 
-    def _prepacked(self, kind, like):
+    def _prepacked(self, kind, like, grad=False):
         """The field kernel's split-fp16 weight packing (row scales, scaled biases,
         MFMA fragments: sdfr_render_*_pack), redone only when a network parameter
-        changed (data pointer or in-place version), not per call."""
+        changed (data pointer or in-place version), not per call.  ``grad``: the SIREN
+        gradient kernel's own packing of the SDF trunk (sdfr_query_siren_grad_pack), kept
+        in a cache entry of its own beside the render's."""
         key = (kind,) + tuple((p.data_ptr(), p._version) for p in self.network.parameters())
-        cache = getattr(self, "_pack_cache", None)
+        attr = "_grad_pack_cache" if grad else "_pack_cache"
+        cache = getattr(self, attr, None)
         if cache is not None and cache[0] == key:
             return cache[1]
         L = _lib.lib()
-        buf = torch.empty(L.sdfr_render_pack_bytes(int(kind)), dtype=torch.uint8,
-                          device=like.device)
-        name = ("sdfr_render_ngp_pack", "sdfr_render_siren_pack", "sdfr_render_fc_pack")[kind]
+        if grad:
+            nbytes, name = L.sdfr_query_siren_grad_pack_bytes(), "sdfr_query_siren_grad_pack"
+        else:
+            nbytes = L.sdfr_render_pack_bytes(int(kind))
+            name = ("sdfr_render_ngp_pack", "sdfr_render_siren_pack", "sdfr_render_fc_pack")[kind]
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=like.device)
         w = self._weight_struct(kind)
         _lib.check(getattr(L, name)(ctypes.byref(w), _lib.ptr(buf), _lib.stream_of(like)), name)
-        self._pack_cache = (key, buf)
+        setattr(self, attr, (key, buf))
         return buf
 
     # ---------------------------------------------------------------- point query
-    # Points per library call of the fused query.  The workspace is about 144 bytes per
+    # Points per library call of the fused query.  The ngp workspace is about 144 bytes per
     # point (the 32 gathered features, the grid coordinate) plus 0.9 MB, so 2^20 points
-    # bound it at ~152 MB; at 32 points per group that is 512 workgroups, two per CU.
+    # bound it at ~152 MB; at 32 points per group that is 512 workgroups, two per CU.  (The
+    # SIREN calls' workspace does not grow with the points; they share the chunking.)
     QUERY_CHUNK_POINTS = 1 << 20
 
     def _query_fused_ok(self, points, styles):
-        """The rule of ``_fused_ok`` for a point query (the fused query exists for the
-        ngp network on the f16x3 field kernel only)."""
-        if self._net_kind() != 0 or self.field_precision != "f16x3":
+        """The rule of ``_fused_ok`` for a point query (the fused query and gradient exist
+        for the ngp and SIREN networks on the f16x3 field kernel; FC stays on the module)."""
+        kind = self._net_kind()
+        if kind not in (0, 1) or self.field_precision != "f16x3":
+            return False
+        if kind == 1 and (self.network.D != 8 or len(self.network.pts_linears) != 8):
             return False
         return self._fused_inputs_ok(points, styles, no_grad_on=(points,))
 
@@ -761,15 +771,20 @@ class VolumeFeatureRenderer(nn.Module):
         not normalised here): ``[B,3]`` one per face, ``[B,M,3]`` one per point, or
         ``None`` with ``return_rgb=False`` (zeros are passed).
 
-        For an ngp network, CUDA tensors, ``field_precision == 'f16x3'`` and no grad
-        needed this runs ``sdfr_query_ngp_forward``: the render's hash-grid gather and
-        split-fp16 field kernel on the given points.  Per-face (or no) directions run in
-        groups of N = 32 points (M padded, the padding trimmed); per-point directions
-        run as M groups of N = 1, which idles the kernel's odd-sample lanes (it takes
-        kRSamples = 2 points of a group per pass), i.e. half rate.  Calls are chunked
-        over groups (``chunk_groups``, default ``QUERY_CHUNK_POINTS`` / N) to bound the
-        workspace; chunking does not change a bit of the result.  Otherwise (SIREN, FC,
-        CPU tensors, the fp32 field, a call under grad) it runs
+        For an ngp or SIREN network, CUDA tensors, ``field_precision == 'f16x3'`` and no
+        grad needed this runs ``sdfr_query_ngp_forward`` / ``sdfr_query_siren_forward``:
+        the render's split-fp16 field kernel (for ngp behind the render's hash-grid
+        gather) on the given points, so a point the render samples gets the render's SDF
+        bit for bit.  Per-face (or no) directions run in groups of N = 32 points (M
+        padded, the padding trimmed); per-point directions run as M groups of N = 1,
+        which idles the kernel's other sample lanes (ngp takes 2 points of a group per
+        pass: half rate; SIREN takes 4: quarter rate).  Calls are chunked over groups
+        (``chunk_groups``, default ``QUERY_CHUNK_POINTS`` / N) to bound the workspace;
+        chunking does not change a bit of the result.  The SIREN kernel splits each
+        coordinate into fp16 hi + lo parts unscaled, as its render does: coordinates
+        must stay below fp16's 65504, and the accuracy tests cover |coordinate| <= 64,
+        the supported range (the render's samples stay below 1.3).  Otherwise (FC, CPU
+        tensors, the fp32 field, a call under grad) it runs
         ``self.network(cat([points, dirs]), styles)``, the autograd path, and slices it.
         """
         if points.dim() != 3 or points.shape[-1] != 3:
@@ -801,9 +816,9 @@ class VolumeFeatureRenderer(nn.Module):
         return sdf, (rgb.reshape(B, R * N, 3)[:, :M] if return_rgb else None)
 
     def _fused_query(self, points, dirs, styles, return_rgb=True, chunk_groups=None):
-        """``sdfr_query_ngp_forward`` on grouped points: ``points`` [B,R,N,3], ``dirs``
-        [B,R,3] (one per group) -> (sdf [B,R,N], rgb [B,R,N,3] | None), in calls of at
-        most ``chunk_groups`` groups per face."""
+        """``sdfr_query_ngp_forward`` / ``sdfr_query_siren_forward`` on grouped points:
+        ``points`` [B,R,N,3], ``dirs`` [B,R,3] (one per group) -> (sdf [B,R,N],
+        rgb [B,R,N,3] | None), in calls of at most ``chunk_groups`` groups per face."""
         self._fused_check_params()
         dev = points.device
         B, R, N = points.shape[:3]
@@ -814,20 +829,24 @@ class VolumeFeatureRenderer(nn.Module):
         if chunk_groups is None:
             chunk_groups = max(16, self.QUERY_CHUNK_POINTS // (B * N) // 16 * 16)
         L = _lib.lib()
-        prepacked = self._prepacked(0, pts)
-        w = self._weight_struct(0)
+        kind = self._net_kind()
+        prepacked = self._prepacked(kind, pts)
+        w = self._weight_struct(kind)
+        Args = (_lib.NgpQueryArgs, _lib.SirenQueryArgs)[kind]
+        name = ("sdfr_query_ngp_forward", "sdfr_query_siren_forward")[kind]
+        ws_bytes = (L.sdfr_query_ngp_workspace_bytes, L.sdfr_query_siren_workspace_bytes)[kind]
+        fn = getattr(L, name)
 
         def call(r, ins, outs, ws):
-            a = _lib.NgpQueryArgs(
+            a = Args(
                 B=B, R=r, N=N, points=_lib.ptr(ins[0]), dirs=_lib.ptr(ins[1]),
                 styles=_lib.ptr(styles), sdf=_lib.ptr(outs[0]), rgb=_lib.ptr(outs[1]),
                 workspace=_lib.ptr(ws), workspace_bytes=ws.numel(),
                 prepacked=_lib.ptr(prepacked))
-            _lib.check(L.sdfr_query_ngp_forward(ctypes.byref(w), ctypes.byref(a),
-                                                _lib.stream_of(pts)), "sdfr_query_ngp_forward")
+            _lib.check(fn(ctypes.byref(w), ctypes.byref(a), _lib.stream_of(pts)), name)
 
         self._chunked_calls(R, chunk_groups, (pts, dirs.float()), (sdf, rgb),
-                            lambda r: L.sdfr_query_ngp_workspace_bytes(B, r, N), call)
+                            lambda r: ws_bytes(B, r, N), call)
         return sdf, rgb
 
     @staticmethod
@@ -869,13 +888,17 @@ class VolumeFeatureRenderer(nn.Module):
         gradient, see ``mesh.eikonal_residual``).  ``normalize=True`` returns
         ``grad / max(|grad|, 1e-20)`` (unit rows; a zero gradient stays zero).
 
-        Under the rule of ``query``'s fused path this runs ``sdfr_query_ngp_grad``: a
-        hash-grid gather that also stores the input derivatives, and a forward-mode
+        Under the rule of ``query``'s fused path this runs ``sdfr_query_ngp_grad`` (ngp:
+        a hash-grid gather that also stores the input derivatives, and a forward-mode
         split-fp16 field kernel over the SDF trunk -- the exact gradient of the piecewise
-        trilinear field, no autograd graph, ``sdf`` bit-identical to ``query``'s.  Calls
+        trilinear field, ``sdf`` bit-identical to ``query``'s) or ``sdfr_query_siren_grad``
+        (SIREN: the same forward-mode kernel over the eight FiLM layers with the point and
+        the three unit vectors as layer 0's columns, on a packing of the trunk of its own;
+        ``sdf`` equals ``query``'s up to fp32 rounding, the accumulation order differs).
+        No autograd graph is built.  Calls
         are chunked over points (``chunk_points`` per face, rounded down to the kernel's
         workgroup pass of 32 points; default ``GRADIENT_CHUNK_POINTS`` / B) to bound the
-        workspace; chunking does not change a bit of the result.  Otherwise (SIREN, FC,
+        workspace; chunking does not change a bit of the result.  Otherwise (FC,
         CPU tensors, the fp32 field, grad mode with a tensor or parameter that requires
         grad) it is ``torch.autograd.grad(sdf.sum(), points)``
         through ``self.network`` with zero view directions, on a detached copy of the
@@ -883,11 +906,15 @@ class VolumeFeatureRenderer(nn.Module):
         caller's ``points`` are left alone.  Either way the result carries no autograd
         graph (an inference query).
 
-        ``encode_only=True`` (fused path only) returns the gather's output instead:
-        ``(features [B,M,32], dy_du [B,M,3,32])``, feature index 2 level + c.
+        ``encode_only=True`` (ngp fused path only) returns the gather's output instead:
+        ``(features [B,M,32], dy_du [B,M,3,32])``, feature index 2 level + c.  A SIREN
+        or FC network has no hash-grid gather: ``ValueError``.
         """
         if points.dim() != 3 or points.shape[-1] != 3:
             raise ValueError(f"query_gradient: points must be [B,M,3], got {tuple(points.shape)}")
+        if encode_only and self._net_kind() != 0:
+            raise ValueError("query_gradient: encode_only returns the ngp hash-grid gather's "
+                             "output; this network has no hash grid")
         fused = self._query_fused_ok(points, styles)
         if encode_only and not fused:
             raise ValueError("query_gradient: encode_only needs the fused path")
@@ -907,8 +934,8 @@ class VolumeFeatureRenderer(nn.Module):
         return sdf, (_unit(grad, -1) if normalize else grad)
 
     def _fused_gradient(self, points, styles, chunk_points=None, encode_only=False):
-        """``sdfr_query_ngp_grad`` on ``points`` [B,M,3] in calls of at most
-        ``chunk_points`` points per face."""
+        """``sdfr_query_ngp_grad`` / ``sdfr_query_siren_grad`` on ``points`` [B,M,3] in
+        calls of at most ``chunk_points`` points per face."""
         self._fused_check_params()
         dev = points.device
         B, M = points.shape[:2]
@@ -922,19 +949,25 @@ class VolumeFeatureRenderer(nn.Module):
         if encode_only:
             chunk_points = max(chunk_points, M)      # one call: its workspace is the result
         L = _lib.lib()
-        prepacked = self._prepacked(0, pts)
-        w = self._weight_struct(0)
+        kind = self._net_kind()
+        # (SIREN: the gradient kernel's own packing of the trunk, cached beside the render's)
+        prepacked = self._prepacked(kind, pts, grad=kind == 1)
+        w = self._weight_struct(kind)
+        Args = (_lib.NgpGradArgs, _lib.SirenGradArgs)[kind]
+        name = ("sdfr_query_ngp_grad", "sdfr_query_siren_grad")[kind]
+        ws_bytes = (L.sdfr_query_ngp_grad_workspace_bytes,
+                    L.sdfr_query_siren_grad_workspace_bytes)[kind]
+        fn = getattr(L, name)
 
         def call(m, ins, outs, ws):
-            a = _lib.NgpGradArgs(
+            a = Args(
                 B=B, M=m, points=_lib.ptr(ins[0]), styles=_lib.ptr(styles),
                 sdf=_lib.ptr(outs[0]), grad=_lib.ptr(outs[1]), workspace=_lib.ptr(ws),
                 workspace_bytes=ws.numel(), prepacked=_lib.ptr(prepacked))
-            _lib.check(L.sdfr_query_ngp_grad(ctypes.byref(w), ctypes.byref(a),
-                                             _lib.stream_of(pts)), "sdfr_query_ngp_grad")
+            _lib.check(fn(ctypes.byref(w), ctypes.byref(a), _lib.stream_of(pts)), name)
 
         ws = self._chunked_calls(M, chunk_points, (pts,), (sdf, grad),
-                                 lambda m: L.sdfr_query_ngp_grad_workspace_bytes(B, m), call)
+                                 lambda m: ws_bytes(B, m), call)
         if encode_only:
             # the workspace starts with the gather's output [B][Mp][4][32], Mp = M up to 8
             Mp = (M + 7) // 8 * 8
@@ -967,7 +1000,8 @@ class VolumeFeatureRenderer(nn.Module):
         ``return_sdf`` output bit for bit), in calls of at most ``chunk_points`` points
         (default ``GRADIENT_CHUNK_POINTS``) over faces and bands of whole image rows; a
         single row above the chunk is one call.  Chunking does not change a bit of any
-        output.  Otherwise (SIREN, FC, CPU tensors, the fp32 field, grad mode with
+        output.  Otherwise (SIREN and FC -- the fused geometry render is ngp's --, CPU
+        tensors, the fp32 field, grad mode with
         something that requires grad) the same definitions are computed op by op, the
         gradient by autograd with grad enabled locally on detached inputs.  Either way the
         result carries no autograd graph.
@@ -979,7 +1013,7 @@ class VolumeFeatureRenderer(nn.Module):
         if unknown or not want:
             raise ValueError(f"render_geometry: want must name some of "
                              f"{self.GEOMETRY_FIELDS}, got {want}")
-        if self._query_fused_ok(cam_poses, styles):
+        if self._net_kind() == 0 and self._query_fused_ok(cam_poses, styles):
             out = self._fused_geometry(cam_poses, focal, near, far, styles, t_rand, want,
                                        chunk_points)
         else:
