@@ -1,5 +1,5 @@
 // field_grad.hip -- the fused ngp SDF and its exact gradient at caller-supplied points
-// (sdfr_query_ngp_grad, host side in render_ngp.hip):
+// (sdfr_query_ngp_grad, sdfr_render_ngp_geometry; entry points in render_api.hip):
 //
 //   ngp_encode_grad_kernel   points [B,M,3] -> gd: per point the 32 hash-grid features and
 //                            their 3 x 32 derivatives with respect to the grid coordinate u
@@ -27,7 +27,7 @@
 //
 // Field kernel: the k-step loop, the LDS-DMA weight ring and the in-register hand-off of
 // activated accumulators as the next layer's B fragments are field_r_kernel's (rstep,
-// field_f16x3.hip), run on the first 2 + 32 slices of the same packed weights with the same
+// field_f16x3_kernels.h), run on the first 2 + 32 slices of the same packed weights with the same
 // FiLM vectors.  A wave's 32 MFMA columns are 8 points x {value, d/du_0, d/du_1, d/du_2},
 // a point's four columns in adjacent lanes (column c = 4 point + kind).  Per accumulator
 // register, with z the GEMM output of the lane's own column and u = fma(gamma'', z_value,
@@ -43,11 +43,9 @@
 // (field_r_kernel's es).  An all-zero column (a point outside the box) keeps exponent 0.
 // The last layer's tangents feed fp32 fmas only and are not rescaled.
 //
-// This unit includes field_f16x3.hip for its templates and helpers alone
-// (SDFR_FIELD_QUERY_TU leaves out its non-template kernels and host code) and instantiates
+// This unit takes field_f16x3_kernels.h for its templates and helpers and instantiates
 // nothing of the render's; it is built with the field kernels' flags.
-#define SDFR_FIELD_QUERY_TU 1
-#include "field_f16x3.hip"
+#include "field_f16x3_kernels.h"
 
 namespace sdfr {
 
@@ -452,34 +450,34 @@ int launch_grad_gather(const sdfr_ngp_weights *w, const float *points, float *gd
     return check_launch("query_ngp_grad: gather");
 }
 
-// xws: the packed weights' region (workspace or the caller's prepacked buffer)
-int launch_gfield_ngp(const sdfr_ngp_weights *w, const char *xws, const float *film,
-                      const float *gd, float *sdf, float *grad, uint32_t B, uint32_t M,
-                      uint32_t Mp, hipStream_t st) {
+// The forward-mode field kernel of a trunk.  xws: the packed weights' region (workspace or
+// the caller's prepacked buffer); in: the ngp gather's gd or the SIREN's points.
+template <class Net>
+static int launch_gfield_net(const NetPtrs &P, const char *xws, const float *film,
+                             const float *in, float *sdf, float *grad, uint32_t B, uint32_t M,
+                             float bound, const char *what, hipStream_t st) {
     GFieldArgs f{};
-    f.gd = gd;
+    f.gd = in;
     f.packed = reinterpret_cast<const f4 *>(xws);
     f.film = film;
-    f.sigma_w = w->sigma_w;
-    f.sigma_b = w->sigma_b;
+    f.sigma_w = P.sigma_w;
+    f.sigma_b = P.sigma_b;
     f.sdf = sdf;
     f.grad = grad;
     f.M = M;
-    f.Mp = Mp;
-    f.bound = w->bound;
+    f.Mp = (M + kGradPts - 1) / kGradPts * kGradPts;
+    f.bound = bound;
     // workgroups of a face take its passes (32 points each) round robin: about four
     // workgroups per CU over the call, every workgroup at least one pass
-    const uint32_t npass = (Mp + kGGroup - 1) / kGGroup;
+    const uint32_t npass = (f.Mp + kGGroup - 1) / kGGroup;
     const uint32_t want = (1024u + B - 1) / B;
     f.wg_per_face = npass < want ? npass : want;
-    hipLaunchKernelGGL(field_g_kernel<NgpGradNet>, dim3(B * f.wg_per_face), dim3(kRThreads), 0, st,
-                       f);
-    return check_launch("query_ngp_grad: field (f16x3)");
+    hipLaunchKernelGGL(field_g_kernel<Net>, dim3(B * f.wg_per_face), dim3(kRThreads), 0, st, f);
+    return check_launch(what);
 }
 
 // ----------------------------------------------------------------------------
-// SIREN: the SDF and its gradient at caller points (sdfr_query_siren_grad, entry points
-// in field_f16x3.hip)
+// SIREN: the SDF and its gradient at caller points (sdfr_query_siren_grad)
 //
 //   xprep_kernel<SirenGradNet>    FiLM vectors of the faces' styles and (once per weight
 //                                 version: sdfr_query_siren_grad_pack) the trunk's weights
@@ -534,25 +532,29 @@ size_t siren_grad_pack_bytes() {
            2 * (size_t)SirenGradNet::kMats * kW * sizeof(float);
 }
 
-int launch_gprep_siren(const sdfr_siren_weights *w, uint32_t B, const float *styles, char *xws,
-                       float *film, bool pack, hipStream_t st) {
+static_assert(SirenGradNet::kFilmN == kSirenGradFilm, "the entry point sizes film with this");
+
+// xprep_kernel on the trunk's eight matrices (P.w[0..7] = pts_linears): launch_xpack's
+// (field_f16x3.hip) steps, with the su | bias_s stride of kMats = 8 rows, not kLayers.
+int launch_gprep_siren(const NetPtrs &P, uint32_t B, const float *styles, char *xws, float *film,
+                       bool pack, hipStream_t st) {
     using Net = SirenGradNet;
     float *su = reinterpret_cast<float *>(xws + (size_t)Net::kSlices * kRSliceF4 * sizeof(f4));
     if (pack) {
         uint32_t K[Net::kMats];
         for (int l = 0; l < Net::kMats; ++l) K[l] = Net::K(l);
-        int rc = launch_xscale(w->pts_w, w->pts_b, K, Net::kMats, su, su + Net::kMats * kW, st);
+        int rc = launch_xscale(P.w, P.b, K, Net::kMats, su, su + Net::kMats * kW, st);
         if (rc) return rc;
     }
     XPrepArgs p{};
     p.styles = styles;
     for (int l = 0; l < Net::kMats; ++l) {
-        p.gw[l] = w->pts_gw[l];
-        p.gb[l] = w->pts_gb[l];
-        p.bw[l] = w->pts_bw[l];
-        p.bb[l] = w->pts_bb[l];
-        p.w[l] = w->pts_w[l];
-        p.lb[l] = w->pts_b[l];
+        p.gw[l] = P.gw[l];
+        p.gb[l] = P.gb[l];
+        p.bw[l] = P.bw[l];
+        p.bb[l] = P.bb[l];
+        p.w[l] = P.w[l];
+        p.lb[l] = P.b[l];
     }
     p.su = su;
     p.film = film;
@@ -565,26 +567,13 @@ int launch_gprep_siren(const sdfr_siren_weights *w, uint32_t B, const float *sty
     return check_launch("query_siren_grad: xprep");
 }
 
-int launch_gfield_siren(const sdfr_siren_weights *w, const char *xws, const float *film,
-                        const float *points, float *sdf, float *grad, uint32_t B, uint32_t M,
-                        hipStream_t st) {
-    GFieldArgs f{};
-    f.gd = points;
-    f.packed = reinterpret_cast<const f4 *>(xws);
-    f.film = film;
-    f.sigma_w = w->sigma_w;
-    f.sigma_b = w->sigma_b;
-    f.sdf = sdf;
-    f.grad = grad;
-    f.M = M;
-    f.Mp = (M + kGradPts - 1) / kGradPts * kGradPts;
-    // as launch_gfield_ngp: a face's passes round robin over about four workgroups per CU
-    const uint32_t npass = (f.Mp + kGGroup - 1) / kGGroup;
-    const uint32_t want = (1024u + B - 1) / B;
-    f.wg_per_face = npass < want ? npass : want;
-    hipLaunchKernelGGL(field_g_kernel<SirenGradNet>, dim3(B * f.wg_per_face), dim3(kRThreads), 0,
-                       st, f);
-    return check_launch("query_siren_grad: field (f16x3)");
+int launch_gfield(int net, const NetPtrs &P, const char *xws, const float *film, const float *in,
+                  float *sdf, float *grad, uint32_t B, uint32_t M, float bound, hipStream_t st) {
+    if (net == kNetNgp)
+        return launch_gfield_net<NgpGradNet>(P, xws, film, in, sdf, grad, B, M, bound,
+                                             "query_ngp_grad: field (f16x3)", st);
+    return launch_gfield_net<SirenGradNet>(P, xws, film, in, sdf, grad, B, M, 0.0f,
+                                           "query_siren_grad: field (f16x3)", st);
 }
 
 }  // namespace sdfr

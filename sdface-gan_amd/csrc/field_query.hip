@@ -1,5 +1,5 @@
-// field_query.hip -- the fused ngp field evaluated at caller-supplied points
-// (sdfr_query_ngp_forward, host side in render_ngp.hip):
+// field_query.hip -- the fused field evaluated at caller-supplied points
+// (sdfr_query_ngp_forward, sdfr_query_siren_forward; entry points in render_api.hip):
 //
 //   query_geom_kernel            points [B,R,N,3] -> gu [S] (grid coordinate, inside flag)
 //                                in the render's tile order with H = 1, W = R
@@ -8,19 +8,16 @@
 //                                read from memory, no compositing, and a per-sample
 //                                store of the SDF and the colour
 //
-// The field kernel is the template of field_f16x3.hip, instantiated HERE and nowhere
+// The field kernel is the template of field_f16x3_kernels.h, instantiated HERE and nowhere
 // else: co-compiled instantiations of one kernel template share register-allocation
 // context, so a query instantiation beside the render's would move the render kernels'
-// code.  This unit includes that source for the templates alone (SDFR_FIELD_QUERY_TU
-// leaves out its non-template kernels and host code) and is built with the same flags.
+// code.  This unit is built with field_f16x3.hip's flags.
 //
-// The SIREN query (sdfr_query_siren_forward, entry point in field_f16x3.hip) is
-// field_p_kernel<SirenQueryNet>, at the end of this file: the render's wave-pair kernel
-// with the point and the group's direction read from memory.  It has no gather and no
-// staging kernel.  field_r_kernel<NgpQueryNet> comes out of the compiler unchanged beside
-// it (profiles/siren_query_isa.txt).
-#define SDFR_FIELD_QUERY_TU 1
-#include "field_f16x3.hip"
+// The SIREN query is field_p_kernel<SirenQueryNet>, at the end of this file: the render's
+// wave-pair kernel with the point and the group's direction read from memory.  It has no
+// gather and no staging kernel.  field_r_kernel<NgpQueryNet> comes out of the compiler
+// unchanged beside it (profiles/siren_query_isa.txt).
+#include "field_f16x3_kernels.h"
 
 namespace sdfr {
 
@@ -70,31 +67,6 @@ int launch_query_geom(const float *points, f4 *gu, const GeomArgs &g, hipStream_
     return check_launch("query_ngp: point geometry");
 }
 
-// g: B faces, H = 1, W = R, N points per group, cam = dirs [B,R,3].  xws: the packed
-// weights' region (workspace or the caller's prepacked buffer).
-int launch_qfield_ngp(const sdfr_ngp_weights *w, const GeomArgs &g, const float *enc,
-                      const char *xws, const float *film, float *sdf, float *rgb,
-                      hipStream_t st) {
-    using Net = NgpQueryNet;
-    XFieldArgs f{};
-    f.g = g;
-    f.enc = enc;
-    f.packed = reinterpret_cast<const f4 *>(xws);
-    f.su = reinterpret_cast<const float *>(xws + (size_t)Net::kSlices * kXSliceF4 * sizeof(f4));
-    f.bias_s = f.su + Net::kLayers * kW;
-    f.film = film;
-    f.sigma_w = w->sigma_w;
-    f.sigma_b = w->sigma_b;
-    f.rgb_w = w->rgb_w;
-    f.rgb_b = w->rgb_b;
-    f.sdf = sdf;
-    f.rgb = rgb;
-    f.nseg = 1;
-    const uint32_t blocks = g.B * ((g.tiles_per_face + kRTiles - 1) / kRTiles);
-    hipLaunchKernelGGL((field_r_kernel<Net>), dim3(blocks), dim3(kRThreads), 0, st, f);
-    return check_launch("query_ngp: field (f16x3)");
-}
-
 // SirenNet in query mode (sdfr_query_siren_forward): field_p_kernel at the caller's points,
 // as NgpQueryNet is field_r_kernel's.  The SIREN has no gather stage, so there is no
 // staging kernel either: a lane reads its point (12 bytes of points [B,R,N,3], passed in
@@ -109,27 +81,26 @@ static_assert(PNet<SirenQueryNet>::kSteps == PNet<SirenNet>::kSteps &&
                   kPSamples == 4,
               "the query runs the render's k-steps on the render's packing");
 
-// g: B faces, H = 1, W = R, N points per group, cam = dirs [B,R,3].
-int launch_qfield_siren(const sdfr_siren_weights *w, const GeomArgs &g, const float *points,
-                        const char *xws, const float *film, float *sdf, float *rgb,
-                        hipStream_t st) {
-    using Net = SirenQueryNet;
+// The field kernel in query mode.  g: B faces, H = 1, W = R, N points per group, cam = dirs
+// [B,R,3]; in: the gathered enc (ngp) or the points [B,R,N,3] (SIREN); xws: the packed
+// weights' region (workspace or the caller's prepacked buffer).
+int launch_qfield(int net, const NetPtrs &P, const GeomArgs &g, const float *in, const char *xws,
+                  const float *film, float *sdf, float *rgb, hipStream_t st) {
     XFieldArgs f{};
     f.g = g;
-    f.enc = points;
-    f.packed = reinterpret_cast<const f4 *>(xws);
-    f.su = reinterpret_cast<const float *>(xws + (size_t)Net::kSlices * kXSliceF4 * sizeof(f4));
-    f.bias_s = f.su + Net::kLayers * kW;
-    f.film = film;
-    f.sigma_w = w->sigma_w;
-    f.sigma_b = w->sigma_b;
-    f.rgb_w = w->rgb_w;
-    f.rgb_b = w->rgb_b;
+    f.enc = in;
     f.sdf = sdf;
     f.rgb = rgb;
     f.nseg = 1;
+    if (net == kNetNgp) {
+        fill_xfield_weights<NgpQueryNet>(f, P, xws, film);
+        const uint32_t blocks = g.B * ((g.tiles_per_face + kRTiles - 1) / kRTiles);
+        hipLaunchKernelGGL((field_r_kernel<NgpQueryNet>), dim3(blocks), dim3(kRThreads), 0, st, f);
+        return check_launch("query_ngp: field (f16x3)");
+    }
+    fill_xfield_weights<SirenQueryNet>(f, P, xws, film);
     const uint32_t blocks = g.B * ((g.tiles_per_face + kPTiles - 1) / kPTiles);
-    hipLaunchKernelGGL((field_p_kernel<Net>), dim3(blocks), dim3(kPThreads), 0, st, f);
+    hipLaunchKernelGGL((field_p_kernel<SirenQueryNet>), dim3(blocks), dim3(kPThreads), 0, st, f);
     return check_launch("query_siren: field (f16x3)");
 }
 

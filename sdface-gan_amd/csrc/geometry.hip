@@ -1,5 +1,5 @@
 // geometry.hip -- the render-time use of the fused SDF gradient (sdfr_render_ngp_geometry,
-// host side in render_ngp.hip): the camera rays' samples go through the gradient call's
+// entry point in render_api.hip): the camera rays' samples go through the gradient call's
 // kernels, and a compositing kernel turns the per-sample SDF and gradient into maps.
 //
 //   geom_points_kernel       cameras -> per sample the network coordinate p_net (what the
@@ -29,6 +29,7 @@
 // accumulators carried in registers across chunks.  The map stores are one ray per lane.
 // One thread per ray reading global memory directly would touch 64 cache lines per wave
 // load (stride 4 N bytes).
+#include "render_launch.h"
 #include "render_ngp.h"
 
 namespace sdfr {

@@ -1,6 +1,7 @@
-// render_ngp.h -- pieces shared by the fused ngp renderer's kernels
-// (render_ngp.hip: prep, hash-grid encode, fp32-MFMA field kernel;
-//  field_f16x3.hip: split-fp16 MFMA field kernel).
+// render_ngp.h -- device helpers and kernel-argument structs shared by the fused
+// renderer's kernel units (render_ngp.hip: prep, hash-grid encode, fp32-MFMA field kernel;
+// field_f16x3_kernels.h: the split-fp16 MFMA field kernels; geometry.hip).  The host-side
+// launch functions those units export are declared in render_launch.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -125,100 +126,6 @@ __device__ __forceinline__ float group_sum(float v) {
     v += __shfl_xor(v, 32);
     return v;
 }
-
-// Split-fp16 field path (field_f16x3.hip).  Its workspace region (`xws`,
-// f16x3_ws_bytes(net): 0 = ngp, 1 = siren) holds the packed fp16 fragments, row
-// scales and scaled biases.
-size_t f16x3_ws_bytes(int net);
-int field_variant();   // profiling ablation selected by sdfr_debug_set_field_variant
-// FiLM vectors of the B faces' styles, and the weight packing into xws unless the caller
-// passed weights packed beforehand (prepacked non-null)
-int launch_xprep_ngp(const sdfr_ngp_weights *w, uint32_t B, const float *styles,
-                     const void *prepacked, char *xws, float *film, hipStream_t st);
-int launch_xfield_ngp(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a,
-                      const GeomArgs &g, const float *enc, char *xws, const float *film,
-                      hipStream_t st, float *part, const float2 *zd);
-// Field query at caller points (field_query.hip): the points' grid coordinates in tile
-// order (g: H = 1, W = R groups, N points per group), and field_r_kernel in query mode
-// (g.cam = dirs [B,R,3]; xws = the packed weights' region; sdf [B,R,N], rgb [B,R,N,3] or
-// null).
-int launch_query_geom(const float *points, f4 *gu, const GeomArgs &g, hipStream_t st);
-int launch_qfield_ngp(const sdfr_ngp_weights *w, const GeomArgs &g, const float *enc,
-                      const char *xws, const float *film, float *sdf, float *rgb,
-                      hipStream_t st);
-// SDF and gradient at caller points (field_grad.hip): the gather with input derivatives
-// (gd [B Mp][4][32], Mp = M rounded up to kGradPts) and the forward-mode field kernel
-// (xws = the packed weights' region; sdf [B,M] or null, grad [B,M,3]).
-constexpr uint32_t kGradPts = 8;             // points per wave pass: the padding unit of M
-constexpr uint32_t kGradPointBytes = 4 * kFeatIn * sizeof(float);   // gd per padded point
-int launch_grad_gather(const sdfr_ngp_weights *w, const float *points, float *gd, uint32_t B,
-                       uint32_t M, uint32_t Mp, hipStream_t st);
-int launch_gfield_ngp(const sdfr_ngp_weights *w, const char *xws, const float *film,
-                      const float *gd, float *sdf, float *grad, uint32_t B, uint32_t M,
-                      uint32_t Mp, hipStream_t st);
-// SIREN field query (field_query.hip): field_p_kernel in query mode on the render's packed
-// weights (g as for launch_qfield_ngp; points [B,R,N,3] network coordinates).
-int launch_qfield_siren(const sdfr_siren_weights *w, const GeomArgs &g, const float *points,
-                        const char *xws, const float *film, float *sdf, float *rgb,
-                        hipStream_t st);
-// SIREN SDF and gradient (field_grad.hip): the SDF trunk in field_r_kernel's packing
-// (siren_grad_pack_bytes(): packed slices | su [8][256] | bias_s [8][256]).
-// launch_gprep_siren: FiLM vectors film [B][8][2][256] and, with `pack`, the row scales
-// and the packing into xws (B = 0, film null: packing only); launch_gfield_siren: the
-// forward-mode field kernel on points [B,M,3].  launch_xscale (field_f16x3.hip): the
-// per-row power-of-two scales of `layers` weight matrices [256][K[l]].
-size_t siren_grad_pack_bytes();
-int launch_xscale(const float *const *w, const float *const *b, const uint32_t *K, int layers,
-                  float *su, float *bias_s, hipStream_t st);
-int launch_gprep_siren(const sdfr_siren_weights *w, uint32_t B, const float *styles, char *xws,
-                       float *film, bool pack, hipStream_t st);
-int launch_gfield_siren(const sdfr_siren_weights *w, const char *xws, const float *film,
-                        const float *points, float *sdf, float *grad, uint32_t B, uint32_t M,
-                        hipStream_t st);
-// Geometry render (geometry.hip): the cameras' samples in plain [B,H,W,N] order as the
-// gradient gather's points (pnet [S,3], zd [S] = (z, dist), S = B H W N), and the
-// compositing of the gradient call's sdf [S] / gnet [S,3] into per-sample eikonal [S,3]
-// and the normal / depth / xyz / mask maps (each output may be null).
-int launch_geom_points(const GeomArgs &g, float *pnet, float2 *zd, hipStream_t st);
-int launch_geom_composite(const GeomArgs &g, const float2 *zd, const float *sdf,
-                          const float *gnet, const float *sigmoid_beta, int force_background,
-                          float *eikonal, float *normal, float *depth, float *xyz, float *mask,
-                          hipStream_t st);
-// sample-segment split of the f16x3 field kernel for small batches
-constexpr uint32_t kFieldSplitMax = 4;   // sample segments per ray at most
-uint32_t field_nseg(uint32_t B, uint32_t tiles_per_face, uint32_t N, int force_background,
-                    uint32_t max_seg);
-size_t field_part_bytes(uint32_t B, uint32_t tiles_per_face, uint32_t N);
-// the camera / sampling fields of a render or geometry call (sdfr_ngp_render_args,
-// sdfr_ngp_geometry_args: the shared fields have the same names)
-template <class Args>
-void fill_geom_args(const Args *a, int static_viewdirs, float bound, GeomArgs &g) {
-    g.B = a->B;
-    g.H = a->H;
-    g.W = a->W;
-    g.N = a->N;
-    g.tiles_per_face = (a->H * a->W + kTileRays - 1) / kTileRays;
-    g.total_tiles = a->B * g.tiles_per_face;
-    g.S_total = g.total_tiles * a->N * kTileRays;
-    g.half_res = (float)a->W * 0.5f;   // get_rays uses out_im_res * .5 for both axes
-    g.cam = a->cam;
-    g.focal = a->focal;
-    g.near_ = a->near_;
-    g.far_ = a->far_;
-    g.pix_x = a->pix_x;
-    g.pix_y = a->pix_y;
-    g.sc.t_vals = a->t_vals;
-    g.sc.t_rand = a->t_rand;
-    g.sc.t_rand_per_sample = a->t_rand_per_sample;
-    g.sc.offset_sampling = a->offset_sampling;
-    g.sc.N = a->N;
-    g.static_viewdirs = static_viewdirs;
-    g.z_normalize = a->z_normalize;
-    g.bound = bound;
-}
-void record_event(void *ev, hipStream_t st);
-// stream waits on a caller's hipEvent_t (NULL: nothing)
-void wait_event(void *ev, hipStream_t st);
 
 // LDS-DMA: buffer resource over [base, base + bytes) (range-checked: offsets past
 // it read zeros) and one 64-lane x 16-B piece from (voff + soff) to the LDS byte

@@ -1,5 +1,9 @@
 // render_ngp.hip -- fused SDF + hash-grid volume renderer for MI355X (gfx950).
 //
+// The kernels of the ngp render's own stages and their launches (the entry point,
+// sdfr_render_ngp_forward, is in render_api.hip), and the camera / sin-probe / ablation
+// entry points, which launch their kernels directly.
+//
 // Replaces VolumeFeatureRenderer.forward for rendering.type == "ngp"
 // (sdf_model.py:411-423 -> render :363 -> render_rays :310 ->
 // NGPSIRENGenerator.forward :1566 -> volume_integration :236) with three
@@ -37,6 +41,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "render_launch.h"
 #include "render_ngp.h"
 
 namespace sdfr {
@@ -791,106 +796,14 @@ __global__ void __launch_bounds__(kThreads, 1) ngp_field_kernel(const FieldArgs 
 }
 
 // ----------------------------------------------------------------------------
-// host side
+// host side: the launches of this unit's kernels (declared in render_launch.h; the render
+// entry points that call them are in render_api.hip)
 // ----------------------------------------------------------------------------
-struct Workspace {
-    float *enc;
-    f4 *packed;
-    float *film;
-};
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// enc [L][S][2] | packed fp32 fragments | film | split-fp16 region (field_f16x3.hip) |
-// segment partials | zd [S] (z, segment length) | gu [S] (grid coordinate, inside flag)
-static size_t ws_layout(uint32_t B, uint32_t H, uint32_t W, uint32_t N, uint32_t L,
-                        size_t *o_packed, size_t *o_film, size_t *o_x = nullptr,
-                        size_t *o_part = nullptr, size_t *o_zd = nullptr,
-                        size_t *o_gu = nullptr) {
-    const size_t tiles = (size_t)B * ((H * W + kTileRays - 1) / kTileRays);
-    const size_t S = tiles * N * kTileRays;
-    size_t off = align256(S * L * 2 * sizeof(float));
-    *o_packed = off;
-    off += align256((size_t)kSlices * kSliceF4 * sizeof(f4));
-    *o_film = off;
-    off += align256((size_t)B * kFilm * 2 * kW * sizeof(float));
-    if (o_x) *o_x = off;
-    off += align256(f16x3_ws_bytes(0));
-    if (o_part) *o_part = off;
-    off += align256(field_part_bytes(B, (H * W + kTileRays - 1) / kTileRays, N));
-    if (o_zd) *o_zd = off;
-    off += align256(S * 2 * sizeof(float));
-    if (o_gu) *o_gu = off;
-    off += align256(S * 4 * sizeof(float));
-    return off;
-}
-
-// The ngp network's shape and weight pointers, for every entry point that takes
-// sdfr_ngp_weights (`who` prefixes the message; need_rgb: the colour head is read too).
-static int check_ngp_weights(const sdfr_ngp_weights *w, const char *who, bool need_rgb) {
-    const std::string p = std::string(who) + ": ";
-    if (w->num_levels != 16)
-        return fail(SDFR_EUNSUPPORTED, p + "fused path needs 16 levels x 2 features");
-    const void *need[] = {w->embeddings, w->offsets, w->input_w, w->input_b, w->views_w,
-                          w->views_b, w->views_gw, w->views_gb, w->views_bw, w->views_bb,
-                          w->sigma_w, w->sigma_b};
-    for (const void *q : need)
-        if (!q) return fail(SDFR_EINVAL, p + "weight pointer is null");
-    if (need_rgb && (!w->rgb_w || !w->rgb_b))
-        return fail(SDFR_EINVAL, p + "weight pointer is null");
-    for (int l = 0; l < 3; ++l)
-        if (!w->pts_w[l] || !w->pts_b[l] || !w->pts_gw[l] || !w->pts_gb[l] || !w->pts_bw[l] ||
-            !w->pts_bb[l])
-            return fail(SDFR_EINVAL, p + "FiLM weight pointer is null");
-    return SDFR_OK;
-}
-
-static int validate(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a) {
-    if (!w || !a) return fail(SDFR_EINVAL, "render_ngp: null args");
-    if (a->B == 0 || a->H == 0 || a->W == 0 || a->N == 0)
-        return fail(SDFR_EINVAL, "render_ngp: empty batch / image / sample count");
-    if (a->field_precision != SDFR_FIELD_F16X3 && a->field_precision != SDFR_FIELD_FP32)
-        return fail(SDFR_EINVAL, "render_ngp: field_precision must be 0 (f16x3) or 1 (fp32)");
-    if (a->max_field_segments > kFieldSplitMax || a->max_field_segments == 3)
-        return fail(SDFR_EINVAL, "render_ngp: max_field_segments must be 0, 1, 2 or 4");
-    if (!a->cam || !a->focal || !a->near_ || !a->far_ || !a->styles || !a->pix_x ||
-        !a->pix_y || !a->t_vals || !a->rgb || !a->workspace)
-        return fail(SDFR_EINVAL, "render_ngp: required pointer is null");
-    if (int rc = check_ngp_weights(w, "render_ngp", true)) return rc;
-    if (a->with_sdf && !w->sigmoid_beta)
-        return fail(SDFR_EINVAL, "render_ngp: sigmoid_beta is required when with_sdf");
-    if (a->features_split) {
-        if (a->field_precision != SDFR_FIELD_F16X3)
-            return fail(SDFR_EUNSUPPORTED, "render_ngp: features_split needs the f16x3 field");
-        if (a->features || !a->features_mod)
-            return fail(SDFR_EINVAL, "render_ngp: features_split takes features_mod and no features");
-    }
-    size_t op, of;
-    if (a->workspace_bytes < ws_layout(a->B, a->H, a->W, a->N, 16, &op, &of))
-        return fail(SDFR_EINVAL, "render_ngp: workspace too small");
-    const uint64_t S = (uint64_t)a->B * ((a->H * a->W + 15) / 16) * a->N * 16;
-    if (S * 16 >= (1ull << 32))
-        return fail(SDFR_EINVAL, "render_ngp: too many samples per call (split the batch)");
-    return SDFR_OK;
-}
-
-static void fill_geom(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, GeomArgs &g) {
-    fill_geom_args(a, a->static_viewdirs, w->bound, g);
-}
-
-void record_event(void *ev, hipStream_t st) {
-    if (ev) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(ev), st);
-}
-
-void wait_event(void *ev, hipStream_t st) {
-    if (ev) (void)hipStreamWaitEvent(st, reinterpret_cast<hipEvent_t>(ev), 0);
-}
-
 #ifdef SDFR_ABLATION
 static int g_field_variant = 0;   // profiling ablations only (see ABL_*)
-int field_variant() { return g_field_variant; }
+static int field_variant() { return g_field_variant; }
 #else
-int field_variant() { return 0; }
+static int field_variant() { return 0; }
 #endif
 
 static void launch_field(int v, dim3 grid, hipStream_t st, const FieldArgs &f) {
@@ -914,9 +827,8 @@ static void launch_field(int v, dim3 grid, hipStream_t st, const FieldArgs &f) {
     }
 }
 
-
-static int launch_prep(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, f4 *packed,
-                       float *film, hipStream_t st) {
+int launch_prep(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, f4 *packed, float *film,
+                hipStream_t st) {
     PrepArgs p;
     p.styles = a->styles;
     for (int l = 0; l < 3; ++l) {
@@ -958,7 +870,7 @@ static void launch_encode_mode(hipStream_t st, const EncodeArgs &e) {
 }
 
 // the per-sample geometry (sample_geom_kernel: gu always, zd when wanted)
-static int launch_geom(const GeomArgs &g, float2 *zd, f4 *gu, hipStream_t st) {
+int launch_geom(const GeomArgs &g, float2 *zd, f4 *gu, hipStream_t st) {
     // samples per thread: all N, split while fewer than 64 k threads would run
     uint32_t spt = g.N;
     while (spt > 1 && (uint64_t)g.total_tiles * kTileRays * ((g.N + spt - 1) / spt) < 65536)
@@ -969,8 +881,8 @@ static int launch_geom(const GeomArgs &g, float2 *zd, f4 *gu, hipStream_t st) {
     return check_launch("render_ngp: sample geometry");
 }
 
-static int launch_encode(const sdfr_ngp_weights *w, const GeomArgs &g, float *enc, const f4 *gu,
-                         hipStream_t st) {
+int launch_encode(const sdfr_ngp_weights *w, const GeomArgs &g, float *enc, const f4 *gu,
+                  hipStream_t st) {
     EncodeArgs e;
     e.g = g;
     e.emb = w->embeddings;
@@ -996,6 +908,37 @@ static int launch_encode(const sdfr_ngp_weights *w, const GeomArgs &g, float *en
     launch_encode_mode<true, true, 1, 1>(st, e);
 #endif
     return check_launch("render_ngp: encode");
+}
+
+size_t fp32_packed_bytes() { return (size_t)kSlices * kSliceF4 * sizeof(f4); }
+
+// the fp32 field kernel on the fragments and FiLM vectors of launch_prep
+int launch_field_fp32(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, const GeomArgs &g,
+                      const float *enc, const f4 *packed, const float *film, hipStream_t st) {
+    FieldArgs f;
+    f.g = g;
+    f.enc = enc;
+    f.packed = packed;
+    f.film = film;
+    f.bias[0] = w->input_b;
+    for (int l = 0; l < 3; ++l) f.bias[1 + l] = w->pts_b[l];
+    f.bias[4] = w->views_b;
+    f.sigma_w = w->sigma_w;
+    f.sigma_b = w->sigma_b;
+    f.rgb_w = w->rgb_w;
+    f.rgb_b = w->rgb_b;
+    f.sigmoid_beta = w->sigmoid_beta;
+    f.sigma_noise = a->sigma_noise;
+    f.force_background = a->force_background;
+    f.with_sdf = a->with_sdf;
+    f.rgb = a->rgb;
+    f.features = a->features;
+    f.sdf = a->sdf;
+    f.xyz = a->xyz;
+    f.mask = a->mask;
+    const uint32_t blocks = (g.total_tiles + kWaves - 1) / kWaves;
+    launch_field(field_variant(), dim3(blocks), st, f);
+    return check_launch("render_ngp: field");
 }
 
 }  // namespace sdfr
@@ -1055,297 +998,4 @@ int sdfr_debug_set_field_variant(int variant) {
                 "sdfr_debug_set_field_variant: variant must be 0,1,2,4,8,15,16,31");
 }
 #endif
-
-size_t sdfr_render_ngp_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t N,
-                                       uint32_t num_levels) {
-    size_t op, of;
-    return ws_layout(B, H, W, N, num_levels, &op, &of);
-}
-
-int sdfr_render_ngp_encode_only(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a,
-                                void *stream) {
-    int rc = validate(w, a);
-    if (rc) return rc;
-    GeomArgs g;
-    fill_geom(w, a, g);
-    size_t o_packed, o_film, o_x, o_part, o_zd, o_gu;
-    ws_layout(a->B, a->H, a->W, a->N, 16, &o_packed, &o_film, &o_x, &o_part, &o_zd, &o_gu);
-    char *ws = reinterpret_cast<char *>(a->workspace);
-    f4 *gu = reinterpret_cast<f4 *>(ws + o_gu);
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = launch_geom(g, nullptr, gu, st))) return rc;
-    return launch_encode(w, g, reinterpret_cast<float *>(ws), gu, st);
-}
-
-int sdfr_render_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a,
-                            void *stream) {
-    int rc = validate(w, a);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    size_t o_packed, o_film, o_x, o_part, o_zd, o_gu;
-    ws_layout(a->B, a->H, a->W, a->N, 16, &o_packed, &o_film, &o_x, &o_part, &o_zd, &o_gu);
-    char *ws = reinterpret_cast<char *>(a->workspace);
-    float *enc = reinterpret_cast<float *>(ws);
-    f4 *packed = reinterpret_cast<f4 *>(ws + o_packed);
-    float *film = reinterpret_cast<float *>(ws + o_film);
-    f4 *gu = reinterpret_cast<f4 *>(ws + o_gu);
-
-    GeomArgs g;
-    fill_geom(w, a, g);
-    record_event(a->stage_events[0], st);
-    if (a->field_precision == SDFR_FIELD_F16X3) {
-        // geometry and gather first (they do not read the styles), then the wait on
-        // the caller's styles (ABI 11), the FiLM prep and the field kernel
-        float2 *zd = reinterpret_cast<float2 *>(ws + o_zd);
-        if ((rc = launch_geom(g, zd, gu, st))) return rc;
-        record_event(a->stage_events[1], st);                  // the encode stage is the gather alone
-        if ((rc = launch_encode(w, g, enc, gu, st))) return rc;
-        record_event(a->stage_events[2], st);
-        wait_event(a->styles_event, st);
-        if ((rc = launch_xprep_ngp(w, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
-            return rc;
-        record_event(a->field_event, st);
-        float *part = reinterpret_cast<float *>(ws + o_part);
-        if ((rc = launch_xfield_ngp(w, a, g, enc, ws + o_x, film, st, part, zd))) return rc;
-        record_event(a->stage_events[3], st);
-        return SDFR_OK;
-    }
-    wait_event(a->styles_event, st);
-    if ((rc = launch_prep(w, a, packed, film, st))) return rc;
-    if ((rc = launch_geom(g, nullptr, gu, st))) return rc;
-    record_event(a->stage_events[1], st);
-    if ((rc = launch_encode(w, g, enc, gu, st))) return rc;
-    record_event(a->stage_events[2], st);
-    record_event(a->field_event, st);
-
-    FieldArgs f;
-    f.g = g;
-    f.enc = enc;
-    f.packed = packed;
-    f.film = film;
-    f.bias[0] = w->input_b;
-    for (int l = 0; l < 3; ++l) f.bias[1 + l] = w->pts_b[l];
-    f.bias[4] = w->views_b;
-    f.sigma_w = w->sigma_w;
-    f.sigma_b = w->sigma_b;
-    f.rgb_w = w->rgb_w;
-    f.rgb_b = w->rgb_b;
-    f.sigmoid_beta = w->sigmoid_beta;
-    f.sigma_noise = a->sigma_noise;
-    f.force_background = a->force_background;
-    f.with_sdf = a->with_sdf;
-    f.rgb = a->rgb;
-    f.features = a->features;
-    f.sdf = a->sdf;
-    f.xyz = a->xyz;
-    f.mask = a->mask;
-    const uint32_t blocks = (g.total_tiles + kWaves - 1) / kWaves;
-    launch_field(field_variant(), dim3(blocks), st, f);
-    if ((rc = check_launch("render_ngp: field"))) return rc;
-    record_event(a->stage_events[3], st);
-    return SDFR_OK;
-}
-
-// ----------------------------------------------------------------------------
-// field query at caller points (ABI 14): the render's gather and f16x3 field stages
-// with the points given instead of sampled along rays, and the per-sample SDF and
-// colour stored instead of composited (kernels: field_query.hip)
-// ----------------------------------------------------------------------------
-// enc [16][S][2] | film [B][4][2][256] | split-fp16 region | gu [S]; S = 0: too many
-// samples for one call
-static size_t query_ws_layout(uint32_t B, uint32_t R, uint32_t N, uint64_t *S_out,
-                              size_t *o_film = nullptr, size_t *o_x = nullptr,
-                              size_t *o_gu = nullptr) {
-    const uint64_t S = (uint64_t)B * (((uint64_t)R + kTileRays - 1) / kTileRays) * N * kTileRays;
-    if (S_out) *S_out = S;
-    size_t off = align256((size_t)S * 16 * 2 * sizeof(float));
-    if (o_film) *o_film = off;
-    off += align256((size_t)B * kFilm * 2 * kW * sizeof(float));
-    if (o_x) *o_x = off;
-    off += align256(f16x3_ws_bytes(0));
-    if (o_gu) *o_gu = off;
-    off += align256((size_t)S * 4 * sizeof(float));
-    return off;
-}
-
-size_t sdfr_query_ngp_workspace_bytes(uint32_t B, uint32_t R, uint32_t N) {
-    return query_ws_layout(B, R, N, nullptr);
-}
-
-int sdfr_query_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_query_args *a,
-                           void *stream) {
-    if (!w || !a) return fail(SDFR_EINVAL, "query_ngp: null args");
-    if (a->B == 0 || a->R == 0 || a->N == 0)
-        return fail(SDFR_EINVAL, "query_ngp: empty batch / group / point count");
-    if (!a->points || !a->dirs || !a->styles || !a->sdf || !a->workspace)
-        return fail(SDFR_EINVAL, "query_ngp: required pointer is null");
-    int rc = check_ngp_weights(w, "query_ngp", true);
-    if (rc) return rc;
-    // the limit of the render (validate: 16 S < 2^32) and the field kernel's 32-bit byte
-    // offsets into enc (128 S < 2^32); group and tile counts fit 32 bits below it
-    uint64_t S;
-    size_t o_film, o_x, o_gu;
-    const size_t need_ws = query_ws_layout(a->B, a->R, a->N, &S, &o_film, &o_x, &o_gu);
-    if (S * 128 >= (1ull << 32) || (uint64_t)a->B * a->R >= (1ull << 32))
-        return fail(SDFR_EINVAL, "query_ngp: too many samples per call (split the points)");
-    if (a->workspace_bytes < need_ws) return fail(SDFR_EINVAL, "query_ngp: workspace too small");
-
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = reinterpret_cast<char *>(a->workspace);
-    float *enc = reinterpret_cast<float *>(ws);
-    float *film = reinterpret_cast<float *>(ws + o_film);
-    f4 *gu = reinterpret_cast<f4 *>(ws + o_gu);
-    GeomArgs g{};
-    g.B = a->B;
-    g.H = 1;
-    g.W = a->R;
-    g.N = a->N;
-    g.tiles_per_face = (a->R + kTileRays - 1) / kTileRays;
-    g.total_tiles = a->B * g.tiles_per_face;
-    g.S_total = (uint32_t)S;
-    g.cam = a->dirs;
-    g.bound = w->bound;
-    if ((rc = launch_query_geom(a->points, gu, g, st))) return rc;
-    if ((rc = launch_encode(w, g, enc, gu, st))) return rc;
-    if ((rc = launch_xprep_ngp(w, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
-        return rc;
-    const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
-    return launch_qfield_ngp(w, g, enc, xws, film, a->sdf, a->rgb, st);
-}
-
-// ----------------------------------------------------------------------------
-// SDF and its gradient at caller points (ABI 15): the gather with input derivatives and
-// the forward-mode f16x3 field kernel on the SDF trunk (kernels: field_grad.hip)
-// ----------------------------------------------------------------------------
-// gd [B Mp][4][32] | film [B][4][2][256] | split-fp16 region; Mp = M rounded up to 8.
-// The kernels index gd in fp32 elements, 128 per padded point, with 32-bit arithmetic:
-// P = B Mp >= 2^25 is too many points for one call (P < 2^64: B < 2^32, Mp <= 2^32), and
-// returns 0 before any byte size is formed.
-constexpr uint64_t kGradMaxPoints = (1ull << 32) / (kGradPointBytes / sizeof(float));
-static size_t grad_ws_layout(uint32_t B, uint32_t M, uint64_t *P_out, size_t *o_film = nullptr,
-                             size_t *o_x = nullptr) {
-    const uint64_t Mp = ((uint64_t)M + kGradPts - 1) / kGradPts * kGradPts;
-    const uint64_t P = (uint64_t)B * Mp;
-    if (P_out) *P_out = P;
-    if (P >= kGradMaxPoints) return 0;
-    size_t off = align256((size_t)P * kGradPointBytes);
-    if (o_film) *o_film = off;
-    off += align256((size_t)B * kFilm * 2 * kW * sizeof(float));
-    if (o_x) *o_x = off;
-    off += align256(f16x3_ws_bytes(0));
-    return off;
-}
-
-size_t sdfr_query_ngp_grad_workspace_bytes(uint32_t B, uint32_t M) {
-    return grad_ws_layout(B, M, nullptr);
-}
-
-int sdfr_query_ngp_grad(const sdfr_ngp_weights *w, const sdfr_ngp_grad_args *a, void *stream) {
-    if (!w || !a) return fail(SDFR_EINVAL, "query_ngp_grad: null args");
-    if (a->B == 0 || a->M == 0) return fail(SDFR_EINVAL, "query_ngp_grad: empty batch / point count");
-    if (!a->points || !a->styles || !a->grad || !a->workspace)
-        return fail(SDFR_EINVAL, "query_ngp_grad: required pointer is null");
-    int rc = check_ngp_weights(w, "query_ngp_grad", false);
-    if (rc) return rc;
-    uint64_t P;
-    size_t o_film = 0, o_x = 0;
-    const size_t need_ws = grad_ws_layout(a->B, a->M, &P, &o_film, &o_x);
-    if (P >= kGradMaxPoints)
-        return fail(SDFR_EINVAL, "query_ngp_grad: too many points per call (split the points)");
-    if (a->workspace_bytes < need_ws)
-        return fail(SDFR_EINVAL, "query_ngp_grad: workspace too small");
-
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = reinterpret_cast<char *>(a->workspace);
-    float *gd = reinterpret_cast<float *>(ws);
-    float *film = reinterpret_cast<float *>(ws + o_film);
-    const uint32_t Mp = (uint32_t)(P / a->B);
-    if ((rc = launch_grad_gather(w, a->points, gd, a->B, a->M, Mp, st))) return rc;
-    if ((rc = launch_xprep_ngp(w, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
-        return rc;
-    const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
-    return launch_gfield_ngp(w, xws, film, gd, a->sdf, a->grad, a->B, a->M, Mp, st);
-}
-
-// ----------------------------------------------------------------------------
-// Geometry render: the gradient call on the cameras' own samples, and normal / depth /
-// xyz / mask maps composited with the render's weights (kernels: geometry.hip)
-// ----------------------------------------------------------------------------
-// the gradient call's workspace for (B, M = H W N) | pnet [P][3] | zd [P] (z, dist) |
-// sdf [P] | gnet [P][3]; P = B Mp padded points, 36 bytes more per padded point.
-// M >= 2^25 alone is too many points (H W N is formed in steps that cannot wrap).
-static size_t geom_ws_layout(uint32_t B, uint32_t H, uint32_t W, uint32_t N, uint32_t *M_out,
-                             size_t *o_film = nullptr, size_t *o_x = nullptr,
-                             size_t *o_pnet = nullptr, size_t *o_zd = nullptr,
-                             size_t *o_sdf = nullptr, size_t *o_gnet = nullptr) {
-    const uint64_t HW = (uint64_t)H * W;
-    if (HW >= kGradMaxPoints || HW * N >= kGradMaxPoints) return 0;
-    const uint32_t M = (uint32_t)(HW * N);
-    if (M_out) *M_out = M;
-    uint64_t P;
-    size_t off = grad_ws_layout(B, M, &P, o_film, o_x);
-    if (P >= kGradMaxPoints) return 0;
-    if (o_pnet) *o_pnet = off;
-    off += align256((size_t)P * 3 * sizeof(float));
-    if (o_zd) *o_zd = off;
-    off += align256((size_t)P * 2 * sizeof(float));
-    if (o_sdf) *o_sdf = off;
-    off += align256((size_t)P * sizeof(float));
-    if (o_gnet) *o_gnet = off;
-    off += align256((size_t)P * 3 * sizeof(float));
-    return off;
-}
-
-size_t sdfr_render_ngp_geometry_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t N) {
-    if (B == 0 || H == 0 || W == 0 || N == 0) return 0;
-    return geom_ws_layout(B, H, W, N, nullptr);
-}
-
-int sdfr_render_ngp_geometry(const sdfr_ngp_weights *w, const sdfr_ngp_geometry_args *a,
-                             void *stream) {
-    if (!w || !a) return fail(SDFR_EINVAL, "render_ngp_geometry: null args");
-    if (a->B == 0 || a->H == 0 || a->W == 0 || a->N == 0)
-        return fail(SDFR_EINVAL, "render_ngp_geometry: empty batch / image / sample count");
-    if (!a->cam || !a->focal || !a->near_ || !a->far_ || !a->styles || !a->pix_x || !a->pix_y ||
-        !a->t_vals || !a->workspace)
-        return fail(SDFR_EINVAL, "render_ngp_geometry: required pointer is null");
-    if (!a->sdf && !a->eikonal && !a->normal && !a->depth && !a->xyz && !a->mask)
-        return fail(SDFR_EINVAL, "render_ngp_geometry: every output is null");
-    int rc = check_ngp_weights(w, "render_ngp_geometry", false);
-    if (rc) return rc;
-    if (!w->sigmoid_beta)
-        return fail(SDFR_EINVAL, "render_ngp_geometry: sigmoid_beta is required (no SDF, no gradient)");
-    uint32_t M = 0;
-    size_t o_film = 0, o_x = 0, o_pnet = 0, o_zd = 0, o_sdf = 0, o_gnet = 0;
-    const size_t need_ws =
-        geom_ws_layout(a->B, a->H, a->W, a->N, &M, &o_film, &o_x, &o_pnet, &o_zd, &o_sdf, &o_gnet);
-    if (need_ws == 0)
-        return fail(SDFR_EINVAL,
-                    "render_ngp_geometry: too many points per call (split the batch or the rows)");
-    if (a->workspace_bytes < need_ws)
-        return fail(SDFR_EINVAL, "render_ngp_geometry: workspace too small");
-
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = reinterpret_cast<char *>(a->workspace);
-    float *gd = reinterpret_cast<float *>(ws);
-    float *film = reinterpret_cast<float *>(ws + o_film);
-    float *pnet = reinterpret_cast<float *>(ws + o_pnet);
-    float2 *zd = reinterpret_cast<float2 *>(ws + o_zd);
-    float *sdf = a->sdf ? a->sdf : reinterpret_cast<float *>(ws + o_sdf);
-    float *gnet = reinterpret_cast<float *>(ws + o_gnet);
-    const uint32_t Mp = (M + kGradPts - 1) / kGradPts * kGradPts;
-    GeomArgs g;
-    fill_geom_args(a, 0, w->bound, g);       // the network's view direction is not read
-    const bool composite = a->eikonal || a->normal || a->depth || a->xyz || a->mask;
-    if ((rc = launch_geom_points(g, pnet, zd, st))) return rc;
-    if ((rc = launch_grad_gather(w, pnet, gd, a->B, M, Mp, st))) return rc;
-    if ((rc = launch_xprep_ngp(w, a->B, a->styles, a->prepacked, ws + o_x, film, st)))
-        return rc;
-    const char *xws = a->prepacked ? reinterpret_cast<const char *>(a->prepacked) : ws + o_x;
-    if ((rc = launch_gfield_ngp(w, xws, film, gd, sdf, gnet, a->B, M, Mp, st))) return rc;
-    if (!composite) return SDFR_OK;
-    return launch_geom_composite(g, zd, sdf, gnet, w->sigmoid_beta, a->force_background,
-                                 a->eikonal, a->normal, a->depth, a->xyz, a->mask, st);
-}
-
 }  // extern "C"

@@ -105,7 +105,7 @@ CASES = [
     ("render_face64", dict(return_sdf=True, return_xyz=True)),
     # hash table at the reference's init scale U(-1e-4, 1e-4) (grid.py:138-140) and a
     # trained-like U(-0.05, 0.05): the split-fp16 layer 0 scales each sample's
-    # features by a power of two before the hi/lo split (field_f16x3.hip feat_scale)
+    # features by a power of two before the hi/lo split (field_f16x3_kernels.h feat_scale)
     ("render_small_tab1e4", {}), ("render_small_tab05", {}),
     ("render_face64_tab1e4", {}), ("render_face64_tab05", {}),
 ]
