@@ -481,6 +481,80 @@ int sdfr_query_siren_grad_pack(const sdfr_siren_weights *w, void *packed, void *
 int sdfr_query_siren_grad(const sdfr_siren_weights *w, const sdfr_siren_grad_args *a,
                           void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Surface render (added to ABI 15 without a version step: additive): per camera ray the
+ * point where the SDF first changes sign from outside to inside, the unit normal and the
+ * field's colour there -- the surface as an image, where the reference's sdf_mesh.py
+ * rasterises a marching-cubes or depth mesh with pytorch3d (sdf_utils.py:209-331).  For the
+ * ngp and the SIREN network; the two entry points share everything but the weights.
+ * The rays and samples z_0..z_{N-1} are those of sdfr_render_*_forward for the same cameras,
+ * t_vals, t_rand and sampling flags; sdf_s is the render's return_sdf output bit for bit.
+ *   1. Bracket.  s* = the smallest s in [0, N-2] with sdf_s > 0 and sdf_{s+1} <= 0.  None
+ *      (N = 1, no sign change, only inside -> outside changes, NaNs) is a miss.  A ray that
+ *      starts inside is not special: the samples before its first positive one are skipped,
+ *      so the hit is where the ray enters the surface again.  a = z_{s*}, b = z_{s*+1},
+ *      fa = sdf_{s*}, fb = sdf_{s*+1}.
+ *   2. Refine, K = refine_steps times (a fixed count, no convergence test: nothing is read
+ *      back, the call can be captured in a graph): m = fmul(0.5, fadd(a, b)),
+ *      p = fadd(o, fmul(d, m)), p_net = fdiv(fmul(p, 2), far - near) under z_normalize, else
+ *      p; f = the SDF sdfr_query_*_forward returns at p_net (points in groups of 32, the
+ *      SDF does not depend on the group's direction); f > 0: a = m, fa = f, else b = m,
+ *      fb = f.
+ *   3. Interpolate.  z* = fadd(a, fmul(fdiv(fa, fsub(fa, fb)), fsub(b, a))) clamped to
+ *      [a, b] (fa > 0 >= fb); the hit point p* and p*_net by the ops of step 2.
+ *   4. Finish.  sdfr_query_*_grad at p*_net gives residual (its SDF there) and g;
+ *      e = fdiv(fmul(g, 2), far - near) under z_normalize, else g (the geometry render's
+ *      eikonal); normal = e / max(|e|, 1e-20).  sdfr_query_*_forward at p*_net with the
+ *      ray's view direction as the render gives it to the network (unit d, or the unit
+ *      camera-frame direction under static_viewdirs), one point per direction, gives rgb.
+ *   5. A miss: every float map 0, sample -1.
+ * Every decision is the sign of an SDF the query call returns, so a caller reproduces the
+ * result exactly from the public calls.  Outputs (each may be NULL, one is required; the
+ * gradient call runs only for normal / residual, the colour call only for rgb, the bracket
+ * and refinement only for a map):
+ *   hit [B,1,H,W] 1.0 / 0.0, sample [B,1,H,W] s* or -1, depth [B,1,H,W] z*, residual
+ *   [B,1,H,W], xyz [B,3,H,W] p* (world), normal [B,3,H,W], rgb [B,3,H,W] in [0,1],
+ *   sdf [B,H,W,N] the coarse SDF.
+ * pix_y may be the renderer's buffer offset by y0 with H = a band of rows (W stays the
+ * image width), as in sdfr_render_ngp_geometry.
+ * Workspace, regions in order, each rounded up to 256 bytes; M = H W, Mp = M rounded up to
+ * 32, S = B M N, rays = B M, P = B Mp:
+ *   the evaluations' region: ngp sdfr_query_ngp_workspace_bytes(B, 16, Pq / 16) with
+ *     Pq = max((M rounded up to 16) N, (Mp / 32 rounded up to 16) 32) padded points per
+ *     face; SIREN sdfr_query_siren_workspace_bytes's
+ *   the gradient's region: sdfr_query_{ngp,siren}_grad_workspace_bytes(B, M)
+ *   sample points [S][3] | (z, dist) [S][2] | coarse sdf [S] (unused when `sdf` is given) |
+ *   brackets [rays][4] | s* [rays] | z* [rays] | midpoints [P][3] | their sdf [P] | hit points
+ *   [rays][3] | directions [rays][3] | gradient call's sdf [rays] and gradient [rays][3] |
+ *   colour call's sdf [rays] and rgb [rays][3]
+ * The size functions return 0 for zero sizes and for sizes the underlying calls cannot
+ * index: M N, Pq or B Pq at or above 2^25 (ngp) or 2^30 (SIREN).
+ * SDFR_EINVAL before any launch for null arguments or required pointers, zero sizes, every
+ * output null, refine_steps > 32, a workspace below the size function's value, or too many
+ * points; SDFR_EUNSUPPORTED for num_levels != 16 (ngp), depth != 8 or width != 256 (SIREN).
+ * sigmoid_beta is not read.  Asynchronous on `stream`; allocates nothing.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfr_surface_args {
+    uint32_t B, H, W, N;              /* faces, image rows, cols, samples per ray           */
+    const float *cam, *focal, *near_, *far_, *styles, *pix_x, *pix_y, *t_vals;
+    const float *t_rand;              /* as sdfr_ngp_render_args; may be NULL               */
+    int t_rand_per_sample, offset_sampling, static_viewdirs, z_normalize;
+    uint32_t refine_steps;            /* K, 0..32; 0 = linear interpolation between samples */
+    float *hit;  int32_t *sample;     /* [B,1,H,W] 1.0/0.0 ; s* or -1                       */
+    float *depth, *residual;          /* [B,1,H,W]                                          */
+    float *xyz, *normal, *rgb;        /* [B,3,H,W]                                          */
+    float *sdf;                       /* [B,H,W,N] coarse SDF, optional                     */
+    void *workspace; size_t workspace_bytes;
+    const void *prepacked;            /* sdfr_render_{ngp,siren}_pack's buffer or NULL      */
+    const void *prepacked_grad;       /* SIREN: sdfr_query_siren_grad_pack's buffer or NULL; */
+                                      /* ngp: ignored                                        */
+} sdfr_surface_args;
+size_t sdfr_render_ngp_surface_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t N);
+size_t sdfr_render_siren_surface_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t N);
+int sdfr_render_ngp_surface(const sdfr_ngp_weights *w, const sdfr_surface_args *a, void *stream);
+int sdfr_render_siren_surface(const sdfr_siren_weights *w, const sdfr_surface_args *a,
+                              void *stream);
+
 #ifdef SDFR_ABLATION
 /* Profiling hooks, exported only by `make ABLATION=1` builds (lib_abl/libsdfr.so,
  * process-global state; never in the product library):

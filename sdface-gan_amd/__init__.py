@@ -18,7 +18,10 @@ VolumeFeatureRenderer.query_gradient / Generator.query_field_gradient (the SDF's
 gradient, fused: sdfr_query_ngp_grad), normal_mesh, eikonal_residual (vertex normals, the
 eikonal check); VolumeFeatureRenderer.render_geometry / Generator.render_geometry -> Geometry
 (the gradient along a render's own rays, normal / depth / xyz maps with the render's weights,
-fused: sdfr_render_ngp_geometry).
+fused: sdfr_render_ngp_geometry); VolumeFeatureRenderer.render_surface /
+Generator.render_surface -> Surface (per ray the SDF's first zero crossing, refined by
+bisection, with the unit normal and the field's colour there, fused:
+sdfr_render_ngp_surface / sdfr_render_siren_surface), shade_surface (a lit view of it).
   SDFOptions, vol_render_opt                            (sdf_utils.py:447, training_utils.py:144)
 Beyond the reference: GraphedGenerator (HIP-graph replay of the inference forward).
 """
@@ -32,10 +35,11 @@ from .generator import (Blur, Decoder, EqualLinear, FusedLeakyReLU, Generator,  
 from .graphs import GraphedGenerator  # noqa: F401
 from .mesh import (Mesh, align_volume, color_mesh, cube_points,  # noqa: F401
                    eikonal_residual, extract_mesh_with_marching_cubes, marching_cubes,
-                   normal_mesh, sdf_cube, world_to_network, xyz2mesh)
+                   normal_mesh, sdf_cube, shade_surface, world_to_network, xyz2mesh)
 from .options import AttrDict, SDFOptions, vol_render_opt  # noqa: F401
 from . import training  # noqa: F401  (stage-2 DDP trainer, Discriminator, losses)
 from .renderer import (FCGenerator, FiLMSiren, Geometry, LinearLayer,  # noqa: F401
-                       NGPSIRENGenerator, SirenGenerator, VolumeFeatureRenderer, get_encoder)
+                       NGPSIRENGenerator, SirenGenerator, Surface, VolumeFeatureRenderer,
+                       get_encoder)
 
 __version__ = "0.1.0"

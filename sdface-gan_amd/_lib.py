@@ -39,6 +39,8 @@ EXPORTS = (
     "sdfr_render_ngp_encode_only", "sdfr_query_ngp_workspace_bytes", "sdfr_query_ngp_forward",
     "sdfr_query_ngp_grad_workspace_bytes", "sdfr_query_ngp_grad",
     "sdfr_render_ngp_geometry_workspace_bytes", "sdfr_render_ngp_geometry",
+    "sdfr_render_ngp_surface_workspace_bytes", "sdfr_render_ngp_surface",
+    "sdfr_render_siren_surface_workspace_bytes", "sdfr_render_siren_surface",
     "sdfr_query_siren_workspace_bytes", "sdfr_query_siren_forward",
     "sdfr_query_siren_grad_workspace_bytes", "sdfr_query_siren_grad_pack_bytes",
     "sdfr_query_siren_grad_pack", "sdfr_query_siren_grad",
@@ -161,6 +163,21 @@ class NgpGeometryArgs(ctypes.Structure):
     ]
 
 
+class SurfaceArgs(ctypes.Structure):
+    """sdfr_surface_args (include/sdfr.h)."""
+    _fields_ = [
+        ("B", _u32), ("H", _u32), ("W", _u32), ("N", _u32),
+        ("cam", _vp), ("focal", _vp), ("near_", _vp), ("far_", _vp), ("styles", _vp),
+        ("pix_x", _vp), ("pix_y", _vp), ("t_vals", _vp), ("t_rand", _vp),
+        ("t_rand_per_sample", _int), ("offset_sampling", _int), ("static_viewdirs", _int),
+        ("z_normalize", _int), ("refine_steps", _u32),
+        ("hit", _vp), ("sample", _vp), ("depth", _vp), ("residual", _vp),
+        ("xyz", _vp), ("normal", _vp), ("rgb", _vp), ("sdf", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
+        ("prepacked", _vp), ("prepacked_grad", _vp),
+    ]
+
+
 class StyledEpilogueArgs(ctypes.Structure):
     """sdfr_styled_epilogue_args (include/sdfr.h)."""
     _fields_ = [
@@ -252,6 +269,12 @@ def lib():
     L.sdfr_render_ngp_geometry_workspace_bytes.argtypes = [_u32, _u32, _u32, _u32]
     L.sdfr_render_ngp_geometry.argtypes = [ctypes.POINTER(NgpWeights),
                                            ctypes.POINTER(NgpGeometryArgs), _vp]
+    for net, weights in (("ngp", NgpWeights), ("siren", SirenWeights)):
+        size = getattr(L, f"sdfr_render_{net}_surface_workspace_bytes")
+        size.restype = ctypes.c_size_t
+        size.argtypes = [_u32, _u32, _u32, _u32]
+        getattr(L, f"sdfr_render_{net}_surface").argtypes = [
+            ctypes.POINTER(weights), ctypes.POINTER(SurfaceArgs), _vp]
     for name in ABLATION_EXPORTS:           # profiling builds only (make ABLATION=1)
         if hasattr(L, name):
             getattr(L, name).argtypes = [_int]

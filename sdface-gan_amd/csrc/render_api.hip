@@ -1,6 +1,7 @@
 // render_api.hip -- the C entry points of the fused renderer (include/sdfr.h): the render of
 // the three networks (ngp, SIREN, FC), the field query and the SDF gradient at caller points
-// (ngp, SIREN), the ngp geometry render, and their packing and workspace-size calls.
+// (ngp, SIREN), the ngp geometry render, the surface render (ngp, SIREN), and their packing
+// and workspace-size calls.
 //
 // Host code only.  An entry point checks its arguments, lays out its workspace and enqueues
 // the stages in order on the caller's stream through the launch functions the kernel units
@@ -170,6 +171,69 @@ FilmWs siren_grad_ws(uint32_t B, uint32_t M) {
     const uint64_t P = (uint64_t)B * (((uint64_t)M + kGradPts - 1) / kGradPts * kGradPts);
     if (P == 0 || P >= kSirenMaxPoints) return FilmWs{};
     return film_ws(B, kSirenGradFilm, siren_grad_pack_bytes(), 0);
+}
+
+// surface render (net: kNetNgp or kNetSiren).  With M = H W rays per face, Mp = M rounded up
+// to 32 (the refinement points, in the query's groups of 32), S = B M N, rays = B M and
+// P = B Mp:
+//   q     the SDF / colour evaluations' sub-workspace.  ngp: the query call's layout for the
+//         largest padded point count per face of its three shapes, Pq = max((M up to 16) N,
+//         (Mp / 32 up to 16) 32) -- ngp_query_ws(B, 16, Pq / 16); SIREN: the query call's
+//   g     the gradient call's sub-workspace for (B, M)
+//   pnet [S][3] | zd [S] (z, dist) | sdf [S] | br [rays] (a, b, fa, fb) | sidx [rays] |
+//   zs [rays] | pts [P][3] | f [P] | hitp [rays][3] | dirs [rays][3] | gsdf [rays] |
+//   ggrad [rays][3] | csdf [rays] | rgbq [rays][3]
+// total 0: too many points.  The coarse pass is the binding count: M N (and Pq, B Pq) must
+// stay below 2^25 padded points for ngp (the query's and the gradient's 32-bit indexing) and
+// below 2^30 for SIREN, the products formed in steps that cannot wrap 64 bits.
+struct SurfWs {
+    uint32_t M, Mp;
+    NgpQueryWs nq;
+    NgpGradWs ng;
+    FilmWs sq, sg;
+    size_t q, g, pnet, zd, sdf, br, sidx, zs, pts, f, hitp, dirs, gsdf, ggrad, csdf, rgbq, total;
+};
+SurfWs surf_ws(int net, uint32_t B, uint32_t H, uint32_t W, uint32_t N) {
+    SurfWs l{};
+    const uint64_t lim = net == kNetNgp ? kGradMaxPoints : kSirenMaxPoints;
+    const uint64_t M = (uint64_t)H * W;
+    if (B == 0 || M == 0 || N == 0 || M >= lim || M * N >= lim) return l;
+    const uint64_t Mp = (M + 31) / 32 * 32;
+    const uint64_t coarse = (M + kTileRays - 1) / kTileRays * kTileRays * N;       // < 2^63
+    const uint64_t refine = (Mp / 32 + kTileRays - 1) / kTileRays * kTileRays * 32;
+    const uint64_t Pq = coarse > refine ? coarse : refine;
+    if (Pq >= lim || (uint64_t)B * Pq >= lim) return l;
+    l.M = (uint32_t)M;
+    l.Mp = (uint32_t)Mp;
+    Regions r;
+    if (net == kNetNgp) {
+        l.nq = ngp_query_ws(B, kTileRays, (uint32_t)(Pq / kTileRays));
+        l.ng = ngp_grad_ws(B, l.M);
+        l.q = r.take(l.nq.total);
+        l.g = r.take(l.ng.total);
+    } else {
+        l.sq = f16x3_render_ws(kNetSiren, B, 0, 0, 0);
+        l.sg = siren_grad_ws(B, l.M);
+        l.q = r.take(l.sq.total);
+        l.g = r.take(l.sg.total);
+    }
+    const size_t S = (size_t)B * M * N, rays = (size_t)B * M, P = (size_t)B * Mp, f = sizeof(float);
+    l.pnet = r.take(S * 3 * f);
+    l.zd = r.take(S * 2 * f);
+    l.sdf = r.take(S * f);
+    l.br = r.take(rays * 4 * f);
+    l.sidx = r.take(rays * f);
+    l.zs = r.take(rays * f);
+    l.pts = r.take(P * 3 * f);
+    l.f = r.take(P * f);
+    l.hitp = r.take(rays * 3 * f);
+    l.dirs = r.take(rays * 3 * f);
+    l.gsdf = r.take(rays * f);
+    l.ggrad = r.take(rays * 3 * f);
+    l.csdf = r.take(rays * f);
+    l.rgbq = r.take(rays * 3 * f);
+    l.total = r.off;
+    return l;
 }
 
 // The split-fp16 weight region of a call: the caller's buffer, packed beforehand
@@ -455,6 +519,154 @@ int check_ngp_render(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, N
     return SDFR_OK;
 }
 
+// ----------------------------------------------------------------------------
+// the surface render's host path, shared by the two networks (SurfNet: what differs)
+// ----------------------------------------------------------------------------
+struct NgpSurf {
+    using Weights = sdfr_ngp_weights;
+    static constexpr int kNet = kNetNgp;
+    static constexpr const char *kWho = "render_ngp_surface";
+    static int check(const Weights *w) { return check_ngp_weights(w, kWho, true); }
+    static NetPtrs ptrs(const Weights *w) { return ngp_ptrs(w); }
+    static float bound(const Weights *w) { return w->bound; }
+};
+struct SirenSurf {
+    using Weights = sdfr_siren_weights;
+    static constexpr int kNet = kNetSiren;
+    static constexpr const char *kWho = "render_siren_surface";
+    static int check(const Weights *w) { return check_siren_weights(w, kWho, true); }
+    static NetPtrs ptrs(const Weights *w) { return siren_ptrs(w); }
+    static float bound(const Weights *) { return 0.0f; }
+};
+
+// What the evaluations of one surface call share: the network, the faces and the query
+// sub-workspace with its FiLM vectors and weight region already prepared.
+template <class SurfNet>
+struct SurfEval {
+    const typename SurfNet::Weights *w;
+    NetPtrs P;
+    uint32_t B;
+    char *q;                       // the query sub-workspace
+    const SurfWs *l;
+    char *xws;                     // the packed weights' region
+    hipStream_t st;
+};
+
+// The field at points [B,R,N,3] with the groups' directions dirs [B,R,3]: sdf [B,R,N] and,
+// when rgb is non-null, the colour [B,R,N,3].  The SDF-only evaluations of the surface
+// render (the coarse pass and every bisection step) pass rgb = nullptr and zero directions:
+// the direction does not enter the SDF.
+template <class SurfNet>
+int sdf_at_points(const SurfEval<SurfNet> &e, uint32_t R, uint32_t N, const float *points,
+                  const float *dirs, float *sdf, float *rgb) {
+    int rc;
+    if constexpr (SurfNet::kNet == kNetNgp) {
+        const uint64_t S = (uint64_t)e.B * ((R + kTileRays - 1) / kTileRays) * N * kTileRays;
+        float *enc = reinterpret_cast<float *>(e.q);
+        const float *film = reinterpret_cast<const float *>(e.q + e.l->nq.film);
+        f4 *gu = reinterpret_cast<f4 *>(e.q + e.l->nq.gu);
+        const GeomArgs g = query_geom(e.B, R, N, S, dirs, e.w->bound);
+        if ((rc = launch_query_geom(points, gu, g, e.st))) return rc;
+        if ((rc = launch_encode(e.w, g, enc, gu, e.st))) return rc;
+        return launch_qfield(kNetNgp, e.P, g, enc, e.xws, film, sdf, rgb, e.st);
+    } else {
+        const uint64_t S = siren_query_padded(e.B, R, N);
+        const GeomArgs g = query_geom(e.B, R, N, S, dirs, 0.0f);
+        return launch_qfield(kNetSiren, e.P, g, points, e.xws,
+                             reinterpret_cast<const float *>(e.q), sdf, rgb, e.st);
+    }
+}
+
+template <class SurfNet>
+int surface_render(const typename SurfNet::Weights *w, const sdfr_surface_args *a,
+                   hipStream_t st) {
+    const char *who = SurfNet::kWho;
+    if (!w || !a) return err(who, SDFR_EINVAL, "null args");
+    if (a->B == 0 || a->H == 0 || a->W == 0 || a->N == 0)
+        return err(who, SDFR_EINVAL, "empty batch / image / sample count");
+    if (any_null({a->cam, a->focal, a->near_, a->far_, a->styles, a->pix_x, a->pix_y, a->t_vals,
+                  a->workspace}))
+        return err(who, SDFR_EINVAL, "required pointer is null");
+    const bool want_grad = a->normal || a->residual;
+    const bool maps = a->hit || a->sample || a->depth || a->xyz || a->rgb || want_grad;
+    if (!a->sdf && !maps) return err(who, SDFR_EINVAL, "every output is null");
+    if (a->refine_steps > 32) return err(who, SDFR_EINVAL, "refine_steps must be 0..32");
+    int rc = SurfNet::check(w);                  // (the field kernel reads the colour head)
+    if (rc) return rc;
+    const SurfWs l = surf_ws(SurfNet::kNet, a->B, a->H, a->W, a->N);
+    if (l.total == 0)
+        return err(who, SDFR_EINVAL, "too many points per call (split the batch or the rows)");
+    if (a->workspace_bytes < l.total) return err(who, SDFR_EINVAL, "workspace too small");
+
+    char *ws = reinterpret_cast<char *>(a->workspace);
+    auto at = [&](size_t off) { return reinterpret_cast<float *>(ws + off); };
+    const uint32_t B = a->B;
+    SurfEval<SurfNet> e;
+    e.w = w;
+    e.P = SurfNet::ptrs(w);
+    e.B = B;
+    e.q = ws + l.q;
+    e.l = &l;
+    e.st = st;
+    float *qfilm;
+    if constexpr (SurfNet::kNet == kNetNgp) {
+        e.xws = weight_region(a->prepacked, e.q + l.nq.x);
+        qfilm = reinterpret_cast<float *>(e.q + l.nq.film);
+    } else {
+        e.xws = weight_region(a->prepacked, e.q + l.sq.x);
+        qfilm = reinterpret_cast<float *>(e.q);
+    }
+    float *sdf = a->sdf ? a->sdf : at(l.sdf);
+    float2 *zd = reinterpret_cast<float2 *>(ws + l.zd);
+    f4 *br = reinterpret_cast<f4 *>(ws + l.br);
+    int32_t *sidx = reinterpret_cast<int32_t *>(ws + l.sidx);
+    float *dirs = at(l.dirs);
+    const GeomArgs g = camera_geom(a, a->static_viewdirs, SurfNet::bound(w));
+
+    // the coarse pass: the render's samples as H W groups of N points, zero directions
+    if (hipMemsetAsync(dirs, 0, (size_t)B * l.M * 3 * sizeof(float), st) != hipSuccess)
+        return err(who, SDFR_ELAUNCH, "zeroing the directions failed");
+    if ((rc = launch_geom_points(g, at(l.pnet), zd, st))) return rc;
+    if ((rc = launch_xprep(SurfNet::kNet, e.P, B, a->styles, e.xws, qfilm,
+                           !a->prepacked, st)))
+        return rc;
+    if ((rc = sdf_at_points(e, l.M, a->N, at(l.pnet), dirs, sdf, nullptr))) return rc;
+    if (!maps) return SDFR_OK;
+    if ((rc = launch_surf_bracket(g, sdf, zd, br, sidx, st))) return rc;
+
+    // K bisection steps on the H W midpoints per face, in groups of 32
+    const float *f = nullptr;
+    for (uint32_t k = 0; k < a->refine_steps; ++k) {
+        if ((rc = launch_surf_step(g, l.Mp, f, br, at(l.pts), st))) return rc;
+        if ((rc = sdf_at_points(e, l.Mp / 32, 32, at(l.pts), dirs, at(l.f), nullptr))) return rc;
+        f = at(l.f);
+    }
+    if ((rc = launch_surf_hit(g, l.Mp, f, br, sidx, at(l.zs), at(l.hitp), dirs, st))) return rc;
+
+    // the gradient and the colour at the hit points, each only when an output needs it
+    if (want_grad) {
+        char *gws = ws + l.g;
+        if constexpr (SurfNet::kNet == kNetNgp) {
+            if ((rc = ngp_gradient(w, B, l.M, at(l.hitp), a->styles, a->prepacked, gws, l.ng,
+                                   at(l.gsdf), at(l.ggrad), st)))
+                return rc;
+        } else {
+            float *gfilm = reinterpret_cast<float *>(gws);
+            char *gx = weight_region(a->prepacked_grad, gws + l.sg.x);
+            if ((rc = launch_gprep_siren(e.P, B, a->styles, gx, gfilm, !a->prepacked_grad, st)))
+                return rc;
+            if ((rc = launch_gfield(kNetSiren, e.P, gx, gfilm, at(l.hitp), at(l.gsdf),
+                                    at(l.ggrad), B, l.M, 0.0f, st)))
+                return rc;
+        }
+    }
+    if (a->rgb &&
+        (rc = sdf_at_points(e, l.M, 1, at(l.hitp), dirs, at(l.csdf), at(l.rgbq))))
+        return rc;
+    return launch_surf_maps(g, sidx, at(l.zs), at(l.gsdf), at(l.ggrad), at(l.rgbq), a->hit,
+                            a->sample, a->depth, a->residual, a->xyz, a->normal, a->rgb, st);
+}
+
 }  // namespace
 }  // namespace sdfr
 
@@ -730,6 +942,28 @@ int sdfr_render_ngp_geometry(const sdfr_ngp_weights *w, const sdfr_ngp_geometry_
     if (!composite) return SDFR_OK;
     return launch_geom_composite(g, zd, sdf, gnet, w->sigmoid_beta, a->force_background,
                                  a->eikonal, a->normal, a->depth, a->xyz, a->mask, st);
+}
+
+// ----------------------------------------------------------------------------
+// Surface render: per camera ray the SDF's first outside -> inside zero crossing, refined
+// by bisection through the query call's kernels, with the normal (gradient call) and the
+// colour (query call) there (ray-side kernels: surface.hip)
+// ----------------------------------------------------------------------------
+size_t sdfr_render_ngp_surface_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t N) {
+    return surf_ws(kNetNgp, B, H, W, N).total;
+}
+
+size_t sdfr_render_siren_surface_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t N) {
+    return surf_ws(kNetSiren, B, H, W, N).total;
+}
+
+int sdfr_render_ngp_surface(const sdfr_ngp_weights *w, const sdfr_surface_args *a, void *stream) {
+    return surface_render<NgpSurf>(w, a, (hipStream_t)stream);
+}
+
+int sdfr_render_siren_surface(const sdfr_siren_weights *w, const sdfr_surface_args *a,
+                              void *stream) {
+    return surface_render<SirenSurf>(w, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

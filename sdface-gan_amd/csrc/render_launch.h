@@ -95,4 +95,25 @@ int launch_geom_composite(const GeomArgs &g, const float2 *zd, const float *sdf,
                           float *eikonal, float *normal, float *depth, float *xyz, float *mask,
                           hipStream_t st);
 
+// ---- surface.hip: the surface render's ray-side kernels -----------------------------
+// rays = B H W.  bracket: the coarse sdf [rays][N] and zd [rays N] (geom_points_kernel's) ->
+// br [rays] = (a, b, fa, fb) and sidx [rays] = s* or -1.  step: the bracket narrowed by f
+// [B][Mp] (the SDF at the previous midpoints; null on the first step), then the next
+// midpoints' network coordinates pts [B][Mp][3]; Mp = H W rounded up to 32, the padding
+// points get the origin.  hit: the last narrowing (f null: none), then zs [rays] = z*, the
+// hit points' network coordinates pnet [rays][3] and the rays' view directions dirs
+// [rays][3].  maps: the [B,C,H,W] outputs (each may be null) from sidx, zs, the gradient
+// call's gsdf [rays] / ggrad [rays][3] and the colour query's rgbq [rays][3] (each read only
+// for the outputs that need it).
+int launch_surf_bracket(const GeomArgs &g, const float *sdf, const float2 *zd, f4 *br,
+                        int32_t *sidx, hipStream_t st);
+int launch_surf_step(const GeomArgs &g, uint32_t Mp, const float *f, f4 *br, float *pts,
+                     hipStream_t st);
+int launch_surf_hit(const GeomArgs &g, uint32_t Mp, const float *f, const f4 *br,
+                    const int32_t *sidx, float *zs, float *pnet, float *dirs, hipStream_t st);
+int launch_surf_maps(const GeomArgs &g, const int32_t *sidx, const float *zs, const float *gsdf,
+                     const float *ggrad, const float *rgbq, float *hit, int32_t *sample,
+                     float *depth, float *residual, float *xyz, float *normal, float *rgb,
+                     hipStream_t st);
+
 }  // namespace sdfr

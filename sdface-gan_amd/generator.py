@@ -887,6 +887,15 @@ class Generator(nn.Module):
         lat0 = self._renderer_latent(styles, truncation, truncation_latent, input_is_latent)
         return self.renderer.render_geometry(cam_poses, focals, near, far, lat0, **kw)
 
+    def render_surface(self, styles, cam_poses, focals, near, far, truncation=1,
+                       truncation_latent=None, input_is_latent=False, **kw):
+        """The surface of the faces of ``styles`` seen from ``cam_poses``: the mapping
+        network and truncation of ``render_geometry``, then
+        ``VolumeFeatureRenderer.render_surface`` (``kw``: t_rand, refine_steps, want,
+        chunk_points) -> ``Surface``.  Not part of the forward graph cache."""
+        lat0 = self._renderer_latent(styles, truncation, truncation_latent, input_is_latent)
+        return self.renderer.render_surface(cam_poses, focals, near, far, lat0, **kw)
+
     def forward(self, styles, cam_poses, focals, near=0.88, far=1.12, return_latents=False,
                 inject_index=None, truncation=1, truncation_latent=None, input_is_latent=False,
                 noise=None, randomize_noise=True, return_sdf=False, return_xyz=False,

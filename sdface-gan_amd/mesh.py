@@ -237,6 +237,25 @@ def eikonal_residual(renderer, styles: torch.Tensor, points: torch.Tensor, near:
     return (g * (2 / (far - near))).norm(dim=-1) - 1
 
 
+def shade_surface(surface, light_dir=(-0.5, 1.0, 5.0), ambient: float = 0.3,
+                  albedo=None) -> torch.Tensor:
+    """A lit view [B, 3, H, W] of a ``Surface`` (``render_surface`` with ``hit`` and
+    ``normal``): ``hit * albedo * (ambient + (1 - ambient) * max(0, n . l))`` with ``l`` the
+    unit vector along ``light_dir`` (world coordinates; the default is the location of the
+    reference's PointLights, sdf_utils.py:209-331, used as a direction).  ``albedo``
+    [B, 3, H, W] or [B, 1, H, W]; ``None`` takes ``surface.rgb``, or white without one.
+    Plain torch: one pass over a few maps."""
+    if surface.hit is None or surface.normal is None:
+        raise ValueError("shade_surface: the surface needs its hit and normal maps")
+    n = surface.normal
+    l = torch.as_tensor(light_dir, dtype=n.dtype, device=n.device)
+    l = (l / l.norm()).view(1, 3, 1, 1)
+    if albedo is None:
+        albedo = surface.rgb if surface.rgb is not None else torch.ones_like(n)
+    lambert = (n * l).sum(1, keepdim=True).clamp_min(0)
+    return surface.hit * albedo.expand_as(n) * (ambient + (1 - ambient) * lambert)
+
+
 def xyz2mesh(xyz: torch.Tensor):
     """Mesh from an expected-surface xyz map [1, 3, H, W] (sdf_utils.py:209):
     Delaunay triangulation of the pixel grid, normals inverted.  Returns

@@ -294,6 +294,12 @@ def _workspace(ws, need, device):
 # eikonal term in forward's layout; fields that were not asked for are None.
 Geometry = namedtuple("Geometry", ("normal", "depth", "xyz", "mask", "sdf", "eikonal"))
 
+# What VolumeFeatureRenderer.render_surface returns: NCHW maps of the SDF's first zero
+# crossing along each ray (``sample`` int32, the others fp32) and the coarse per-sample SDF
+# in forward's layout; fields that were not asked for are None.
+Surface = namedtuple("Surface", ("hit", "sample", "depth", "xyz", "normal", "rgb", "residual",
+                                 "sdf"))
+
 
 class VolumeFeatureRenderer(nn.Module):
     """Drop-in for sdf_model.py:143-423 (same options, buffers, outputs)."""
@@ -1119,6 +1125,221 @@ class VolumeFeatureRenderer(nn.Module):
                 for k, fn in maps.items():
                     if k in want:
                         out[k] = fn().permute(0, 3, 1, 2).contiguous()
+        return out
+
+    # ---------------------------------------------------------------- surface render
+    SURFACE_FIELDS = Surface._fields
+    # Samples per library call of the fused surface render.  A bisection step evaluates only
+    # H W points per face, a few workgroups' worth, so a call should hold as many faces as
+    # it can: 2^22 samples take 32 faces of 64^2 x 24 or one of 128^2 x 128 in one call (four
+    # calls of 2^20 samples took twice as long).  The ngp workspace is about 170 bytes per
+    # sample, ~0.7 GB at this bound; the SIREN's about 25.
+    SURFACE_CHUNK_POINTS = 1 << 22
+
+    def render_surface(self, cam_poses, focal, near, far, styles, t_rand=None, refine_steps=8,
+                       want=("hit", "depth", "xyz", "normal", "rgb"), chunk_points=None):
+        """The surface itself as an image: ``Surface(hit, sample, depth, xyz, normal, rgb,
+        residual, sdf)`` for the cameras of ``forward``; fields not named in ``want`` are
+        ``None``.  Per ray (the definition is pinned in include/sdfr.h):
+
+        1. *Bracket*: ``s*`` is the first sample with ``sdf_s > 0`` and ``sdf_{s+1} <= 0``
+           (outside -> inside) among the render's own samples and SDF.  No such sample is a
+           miss.  A ray that starts inside the surface is not special-cased: its samples up
+           to the first positive one are skipped, so it reports where it enters again.
+        2. *Refine*: ``refine_steps`` (0..32) bisection steps on ``[z_s*, z_s*+1]``, the SDF
+           of each midpoint being exactly what ``query`` returns there.  The count is fixed
+           (no convergence test, no host synchronisation).
+        3. *Interpolate*: ``z*`` linearly between the final bracket's ends, clamped to it.
+        4. *Finish*: ``residual`` is ``query_gradient``'s SDF at the hit point, ``normal``
+           its gradient with respect to the world point divided by ``max(|.|, 1e-20)``,
+           ``rgb`` is ``query``'s colour there (in [0,1]) with the view direction the
+           render gives the network for the ray.
+
+        ``hit`` [B,1,H,W] is 1.0 / 0.0, ``sample`` [B,1,H,W] int32 is ``s*`` or -1, ``depth``
+        [B,1,H,W] is ``z*``, ``xyz`` [B,3,H,W] the world point ``o + d z*``, ``normal`` and
+        ``rgb`` [B,3,H,W], ``sdf`` [B,H,W,N,1] the coarse SDF in forward's layout.  On a
+        miss every float map is 0.  The sampling flags are the renderer's; ``t_rand`` is
+        drawn as in ``forward`` when ``perturb > 0`` and none is given.
+
+        Under the rule of ``query``'s fused path (ngp and SIREN) this runs
+        ``sdfr_render_ngp_surface`` / ``sdfr_render_siren_surface`` in calls of at most
+        ``chunk_points`` samples (default ``SURFACE_CHUNK_POINTS``) over faces and bands of
+        whole image rows; rays are independent, so chunking does not change a bit.
+        Otherwise (FC, CPU tensors, the fp32 field, grad mode with something that requires
+        grad) ``_module_surface`` computes the same definition op by op on
+        ``self.network``.  Either way the result carries no autograd graph.
+        """
+        if not self.with_sdf:
+            raise ValueError("render_surface: the renderer has no SDF (no_sdf)")
+        want = tuple(want)
+        unknown = [k for k in want if k not in self.SURFACE_FIELDS]
+        if unknown or not want:
+            raise ValueError(f"render_surface: want must name some of "
+                             f"{self.SURFACE_FIELDS}, got {want}")
+        refine_steps = int(refine_steps)
+        if not 0 <= refine_steps <= 32:
+            raise ValueError(f"render_surface: refine_steps must be 0..32, got {refine_steps}")
+        path = (self._fused_surface if self._query_fused_ok(cam_poses, styles)
+                else self._module_surface)
+        out = path(cam_poses, focal, near, far, styles, t_rand, refine_steps, want, chunk_points)
+        return Surface(**{k: out.get(k) for k in self.SURFACE_FIELDS})
+
+    def _fused_surface(self, cam_poses, focal, near, far, styles, t_rand, refine_steps, want,
+                       chunk_points):
+        """``sdfr_render_{ngp,siren}_surface`` in calls of whole faces or bands of rows."""
+        self._fused_check_params()
+        dev = cam_poses.device
+        B = cam_poses.shape[0]
+        H = W = self.out_im_res
+        N = self.N_samples
+        cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals = \
+            self._fused_inputs(cam_poses, focal, near, far, styles, t_rand)
+        shapes = {k: (B, 3 if k in ("xyz", "normal", "rgb") else 1, H, W)
+                  for k in self.SURFACE_FIELDS}
+        shapes["sdf"] = (B, H, W, N)
+        out = {k: torch.empty(shapes[k], device=dev,
+                              dtype=torch.int32 if k == "sample" else torch.float32)
+               for k in want}
+        if chunk_points is None:
+            chunk_points = self.SURFACE_CHUNK_POINTS
+        chunk_points = max(1, int(chunk_points))
+        per_row, per_face = W * N, H * W * N
+        if per_face <= chunk_points:
+            faces, rows = max(1, chunk_points // per_face), H
+        else:
+            faces, rows = 1, max(1, chunk_points // per_row)
+        L = _lib.lib()
+        kind = self._net_kind()
+        net = ("ngp", "siren")[kind]
+        fn = getattr(L, f"sdfr_render_{net}_surface")
+        ws_bytes = getattr(L, f"sdfr_render_{net}_surface_workspace_bytes")
+        prepacked = self._prepacked(kind, cam)
+        needs_grad = kind == 1 and ("normal" in want or "residual" in want)
+        prepacked_grad = self._prepacked(kind, cam, grad=True) if needs_grad else None
+        w = self._weight_struct(kind)
+        ws = None
+        for b0 in range(0, B, faces):
+            b1 = min(B, b0 + faces)
+            for y0 in range(0, H, rows):
+                y1 = min(H, y0 + rows)
+                # the coarse SDF of a band is contiguous in the result; a band of a map is
+                # not: it goes through a tensor of its own
+                dst, tmp = {}, {}
+                for k, t in out.items():
+                    v = t[b0:b1, y0:y1] if k == "sdf" else t[b0:b1, :, y0:y1]
+                    dst[k] = v if v.is_contiguous() else torch.empty(v.shape, device=dev,
+                                                                     dtype=v.dtype)
+                    if dst[k] is not v:
+                        tmp[k] = v
+                c_rand = None
+                if t_rand is not None:
+                    c_rand = t_rand[b0:b1, y0:y1].contiguous()
+                need = ws_bytes(b1 - b0, y1 - y0, W, N)
+                if need == 0:
+                    raise ValueError("render_surface: too many points in one call; lower "
+                                     "chunk_points")
+                ws = _workspace(ws, need, dev)
+                c_y = pix_y[y0:y1]
+                a = _lib.SurfaceArgs(
+                    B=b1 - b0, H=y1 - y0, W=W, N=N, cam=_lib.ptr(cam[b0:b1]),
+                    focal=_lib.ptr(focal[b0:b1]), near_=_lib.ptr(near[b0:b1]),
+                    far_=_lib.ptr(far[b0:b1]), styles=_lib.ptr(styles[b0:b1]),
+                    pix_x=_lib.ptr(pix_x), pix_y=_lib.ptr(c_y), t_vals=_lib.ptr(t_vals),
+                    t_rand=_lib.ptr(c_rand), t_rand_per_sample=per_sample,
+                    offset_sampling=int(self.offset_sampling),
+                    static_viewdirs=int(bool(self.static_viewdirs)),
+                    z_normalize=int(self.z_normalize), refine_steps=refine_steps,
+                    workspace=_lib.ptr(ws), workspace_bytes=ws.numel(),
+                    prepacked=_lib.ptr(prepacked), prepacked_grad=_lib.ptr(prepacked_grad),
+                    **{k: _lib.ptr(dst.get(k)) for k in self.SURFACE_FIELDS})
+                _lib.check(fn(ctypes.byref(w), ctypes.byref(a), _lib.stream_of(cam)),
+                           f"sdfr_render_{net}_surface")
+                for k, v in tmp.items():
+                    v.copy_(dst[k])
+        if "sdf" in out:
+            out["sdf"] = out["sdf"].unsqueeze(-1)
+        return out
+
+    def _module_surface(self, cam_poses, focal, near, far, styles, t_rand, refine_steps, want,
+                        chunk_points=None):
+        """``render_surface`` op by op on ``self.network``: the definition in code.  Every
+        line is one rounded fp32 operation of the definition's chain; the gradient is
+        autograd's, with grad enabled locally on detached inputs."""
+        cam_poses, focal, near, far = (t.detach() for t in (cam_poses, focal, near, far))
+        styles = styles.detach() if styles is not None else None
+        with torch.no_grad():
+            rays_o, rays_d, viewdirs, near, far = (
+                t.float() for t in self.camera_rays(focal, cam_poses, near, far))
+            z_vals, _, normalized_pts = self.sample_points(rays_o, rays_d, near, far, t_rand,
+                                                           self._stratify())
+            sdf = self.run_network(normalized_pts, viewdirs, styles=styles)[..., 3]
+            N = sdf.shape[-1]
+            span = far - near                                      # [B,H,W,1]
+
+            def network_point(z):
+                p = rays_o + rays_d * z.unsqueeze(-1)
+                return p, (p * 2 / span if self.z_normalize else p)
+
+            def field(p_net):
+                return self.network(torch.cat([p_net, viewdirs], -1), styles=styles)
+
+            # 1. bracket: the first s with sdf_s > 0 >= sdf_{s+1}
+            if N > 1:
+                cross = (sdf[..., :-1] > 0) & (sdf[..., 1:] <= 0)
+                steps = torch.arange(N - 1, device=sdf.device).expand(cross.shape)
+                first = torch.where(cross, steps, torch.full_like(steps, N)).min(-1).values
+            else:
+                first = torch.full(sdf.shape[:-1], N, dtype=torch.long, device=sdf.device)
+            hit = first < N
+            s0 = torch.where(hit, first, torch.zeros_like(first)).unsqueeze(-1)
+            s1 = (s0 + 1).clamp_max(N - 1)
+            a, b = z_vals.expand(sdf.shape).gather(-1, s0)[..., 0], \
+                z_vals.expand(sdf.shape).gather(-1, s1)[..., 0]
+            fa, fb = sdf.gather(-1, s0)[..., 0], sdf.gather(-1, s1)[..., 0]
+            # 2. refine: a fixed number of bisection steps
+            for _ in range(refine_steps):
+                m = 0.5 * (a + b)
+                f = field(network_point(m)[1])[..., 3]
+                pos = f > 0
+                a, fa = torch.where(pos, m, a), torch.where(pos, f, fa)
+                b, fb = torch.where(pos, b, m), torch.where(pos, fb, f)
+            # 3. interpolate (a miss keeps a valid point: its bracket's near end)
+            t = torch.where(hit, fa / (fa - fb), torch.zeros_like(fa))
+            z = torch.minimum(torch.maximum(a + t * (b - a), a), b)
+            p, p_net = network_point(z)
+        mask = hit.unsqueeze(1)                                    # [B,1,H,W]
+
+        def nchw(v):
+            v = v.unsqueeze(-1) if v.dim() == 3 else v
+            v = v.permute(0, 3, 1, 2)
+            return torch.where(mask, v, torch.zeros_like(v)).contiguous()
+
+        out = {}
+        if "sdf" in want:
+            out["sdf"] = sdf.unsqueeze(-1)
+        if "hit" in want:
+            out["hit"] = mask.float()
+        if "sample" in want:
+            out["sample"] = torch.where(hit, first, -torch.ones_like(first)).int().unsqueeze(1)
+        if "depth" in want:
+            out["depth"] = nchw(z)
+        if "xyz" in want:
+            out["xyz"] = nchw(p)
+        # 4. finish
+        if "normal" in want or "residual" in want:
+            with torch.enable_grad():
+                pts = p_net.detach().clone().requires_grad_(True)
+                res = self.network(torch.cat([pts, torch.zeros_like(pts)], -1),
+                                   styles=styles)[..., 3]
+                g, = torch.autograd.grad(res.sum(), pts)
+            e = g * 2 / span if self.z_normalize else g
+            if "residual" in want:
+                out["residual"] = nchw(res.detach())
+            if "normal" in want:
+                out["normal"] = nchw(_unit(e, -1))
+        if "rgb" in want:
+            with torch.no_grad():
+                out["rgb"] = nchw(torch.sigmoid(field(p_net)[..., :3]))
         return out
 
     # ---------------------------------------------------------------- API
