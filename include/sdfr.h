@@ -482,6 +482,92 @@ int sdfr_query_siren_grad(const sdfr_siren_weights *w, const sdfr_siren_grad_arg
                           void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Fused FC field query at caller-supplied points (added to ABI 15 without a version step:
+ * additive, nothing existing changes; no reference native op: replaces
+ * FCGenerator.forward, sdf_model.py:1599-1670, evaluated op by op on cat([points, dirs])).
+ * The field kernel of sdfr_render_fc_forward with the caller's points in place of the ray
+ * sampler and a per-sample store in place of compositing: the same packed weights
+ * (`prepacked` is sdfr_render_fc_pack's buffer; NULL packs into the workspace), FiLM slots
+ * (1/su and the bias, layer 0's bias per face including style_in(styles)), k-step order
+ * and per-sample arithmetic.  The point is halved exactly as the render halves its sample
+ * (RN(p / 2)) before the 60 positional encodings, so a point the render samples gets the
+ * render's SDF bit for bit.
+ * The fields mean what sdfr_siren_query_args' mean: points are NETWORK coordinates, the N
+ * points of a group share one direction, directions are as the network sees them and are
+ * not renormalised.  There is no grid box: every point runs through the same arithmetic.
+ * Rate: a wave of the kernel takes kRSamples = 2 points of each of 16 groups per pass, so
+ * N = 1 (a direction per point) idles half of its columns; even N runs at the full rate.
+ * The colour head runs whether or not rgb is wanted.
+ * Coordinate range: the encodings' arguments are the fp32 module's own (2^i pi p / 2,
+ * reduced in fp64), so any finite coordinate is evaluated as the module evaluates it; the
+ * accuracy bounds of the test-suite are checked for |coordinate| <= 2.2.
+ * Workspace: 18 KiB of FiLM slots per face + the weight-packing region
+ * (sdfr_render_pack_bytes(2)); it does not grow with the point count.
+ * SDFR_EINVAL before any launch for null arguments or required pointers, a null weight
+ * pointer, zero sizes, a workspace below sdfr_query_fc_workspace_bytes(B, R, N), or 2^30
+ * or more padded points B x (R rounded up to 16) x N in one call (the kernel forms
+ * group, tile and padded-sample indices in 32 bits; the limit is the SIREN call's, which
+ * keeps all of them in range; the size function returns 0 for such a size, and for
+ * products that wrap); SDFR_EUNSUPPORTED for depth != 8 or width != 256.
+ * Asynchronous on `stream`; allocates nothing.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfr_fc_query_args {
+    uint32_t B, R, N;        /* faces; direction groups per face; points per group  */
+    const float *points;     /* [B,R,N,3] network coordinates                        */
+    const float *dirs;       /* [B,R,3] direction of each group as the network sees  */
+                             /* it (not normalised again)                            */
+    const float *styles;     /* [B,256] renderer latent                              */
+    float *sdf;              /* [B,R,N]   sigma_linear output           (required)   */
+    float *rgb;              /* [B,R,N,3] sigmoid(rgb_linear) in [0,1], or NULL      */
+    void *workspace; size_t workspace_bytes;
+    const void *prepacked;   /* sdfr_render_fc_pack's buffer, or NULL                */
+} sdfr_fc_query_args;
+size_t sdfr_query_fc_workspace_bytes(uint32_t B, uint32_t R, uint32_t N);
+int sdfr_query_fc_forward(const sdfr_fc_weights *w, const sdfr_fc_query_args *a, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Fused FC SDF and its exact gradient at caller-supplied points (added to ABI 15 without a
+ * version step; replaces autograd through FCGenerator's SDF trunk).  The forward-mode
+ * split-fp16 field kernel of sdfr_query_ngp_grad over x_in, pts_linears.0-6 and
+ * sigma_linear (no views layer, no colour): a wave's 32 MFMA columns are 8 points x
+ * {value, d/dx, d/dy, d/dz}.  Layer 0's value column holds the 60 encodings as the render
+ * forms them; tangent column k holds their derivatives with respect to coordinate k,
+ * + cos(arg) c_i / 2 for a sine entry and - sin(arg) c_i / 2 for a cosine entry, with the
+ * module's own fp32 argument arg = RN(c_i RN(p_k / 2)), c_i = RN32(2^i pi).  Every layer is
+ * ReLU: a tangent passes (1/su) z where the value's pre-activation is > 0 and is 0
+ * elsewhere -- at exactly 0 the derivative is 0, as torch.relu's backward has it.  The
+ * gradient is that of the piecewise linear trunk on the point's own piece; it jumps
+ * where a pre-activation changes sign.  Tangent columns are rescaled by a power of two per
+ * layer and the exponent is undone exactly at the end, so gradients of any magnitude
+ * (1e-8 with nearly dead late layers, 1e+3) keep fp32's relative accuracy.
+ * grad is d sdf / d point in NETWORK coordinates.
+ * The trunk is the first 116 slices of the render's packing: `prepacked` is
+ * sdfr_render_fc_pack's buffer, the same one sdfr_query_fc_forward takes; NULL packs into
+ * the workspace on every call.  The FiLM slots are the render's.
+ * sdf (optional) is sdfr_query_fc_forward's SDF bit for bit: the value columns run the
+ * same slices in the same k-step order on unscaled inputs.
+ * Workspace: 18 KiB of FiLM slots per face + the weight-packing region
+ * (sdfr_render_pack_bytes(2)); it does not grow with the point count.  SDFR_EINVAL before
+ * any launch for null arguments or required pointers, a null weight pointer (all of
+ * sdfr_fc_weights' but sigmoid_beta: packing reads the views layer too), zero sizes, a
+ * workspace below sdfr_query_fc_grad_workspace_bytes(B, M), or 2^30 or more padded points
+ * B x (M rounded up to 8) in one call (the limit of the query call, kept for both; the
+ * size function returns 0 for such a size); SDFR_EUNSUPPORTED for depth != 8 or
+ * width != 256.  Asynchronous; allocates nothing.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfr_fc_grad_args {
+    uint32_t B, M;            /* faces; points per face                        */
+    const float *points;      /* [B,M,3] network coordinates                   */
+    const float *styles;      /* [B,256]                                       */
+    float *sdf;               /* [B,M] or NULL                                 */
+    float *grad;              /* [B,M,3] d sdf / d point (network coordinates) */
+    void *workspace; size_t workspace_bytes;
+    const void *prepacked;    /* sdfr_render_fc_pack's buffer, or NULL         */
+} sdfr_fc_grad_args;
+size_t sdfr_query_fc_grad_workspace_bytes(uint32_t B, uint32_t M);
+int sdfr_query_fc_grad(const sdfr_fc_weights *w, const sdfr_fc_grad_args *a, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Surface render (added to ABI 15 without a version step: additive): per camera ray the
  * point where the SDF first changes sign from outside to inside, the unit normal and the
  * field's colour there -- the surface as an image, where the reference's sdf_mesh.py

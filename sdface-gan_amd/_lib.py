@@ -49,6 +49,8 @@ EXPORTS = (
     "sdfr_render_siren_workspace_bytes", "sdfr_render_siren_forward",
     "sdfr_render_pack_bytes", "sdfr_render_ngp_pack", "sdfr_render_siren_pack",
     "sdfr_render_fc_workspace_bytes", "sdfr_render_fc_forward", "sdfr_render_fc_pack",
+    "sdfr_query_fc_workspace_bytes", "sdfr_query_fc_forward",
+    "sdfr_query_fc_grad_workspace_bytes", "sdfr_query_fc_grad",
     "sdfr_fused_bias_act", "sdfr_mapping_linear", "sdfr_decoder_styles", "sdfr_upfirdn2d", "sdfr_styled_epilogue", "sdfr_modulate_to_nhwc",
     "sdfr_modulate_to_nhwc_split",
     "sdfr_conv_pack_bytes", "sdfr_conv_pack_weights", "sdfr_conv3x3_f16x3",
@@ -146,6 +148,16 @@ class SirenQueryArgs(ctypes.Structure):
 
 class SirenGradArgs(ctypes.Structure):
     """sdfr_siren_grad_args (include/sdfr.h)."""
+    _fields_ = list(NgpGradArgs._fields_)
+
+
+class FcQueryArgs(ctypes.Structure):
+    """sdfr_fc_query_args (include/sdfr.h)."""
+    _fields_ = list(NgpQueryArgs._fields_)
+
+
+class FcGradArgs(ctypes.Structure):
+    """sdfr_fc_grad_args (include/sdfr.h)."""
     _fields_ = list(NgpGradArgs._fields_)
 
 
@@ -302,6 +314,14 @@ def lib():
     L.sdfr_render_fc_pack.argtypes = [ctypes.POINTER(FcWeights), _vp, _vp]
     L.sdfr_render_fc_forward.argtypes = [ctypes.POINTER(FcWeights),
                                          ctypes.POINTER(NgpRenderArgs), _vp]
+    L.sdfr_query_fc_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_query_fc_workspace_bytes.argtypes = [_u32, _u32, _u32]
+    L.sdfr_query_fc_forward.argtypes = [ctypes.POINTER(FcWeights),
+                                        ctypes.POINTER(FcQueryArgs), _vp]
+    L.sdfr_query_fc_grad_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_query_fc_grad_workspace_bytes.argtypes = [_u32, _u32]
+    L.sdfr_query_fc_grad.argtypes = [ctypes.POINTER(FcWeights),
+                                     ctypes.POINTER(FcGradArgs), _vp]
     L.sdfr_debug_sin_probe.argtypes = [_vp, _vp, _vp, _u32, _vp]
     L.sdfr_debug_sin_rev_probe.argtypes = [_vp, _vp, _u32, _vp]
     L.sdfr_camera_extrinsics.argtypes = [_vp, _vp, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp,

@@ -110,7 +110,9 @@ struct NgpQueryNet : NgpNet {
 };
 // (SirenNet's query policy, SirenQueryNet, puts field_p_kernel into the same mode -- the
 // points [B,R,N,3] arrive in XFieldArgs::enc, which the SIREN render leaves unused; it is
-// declared where it is instantiated, csrc/field_query.hip.)
+// declared where it is instantiated, csrc/field_query.hip.  FcNet's, FcQueryNet, is
+// field_r_kernel's as NgpQueryNet is, with the point read from XFieldArgs::enc as well; it
+// is declared and instantiated in csrc/field_fc_query.hip.)
 
 // field_p_kernel's packing (SirenNet): slices = 2 per k-step of 32 input features
 // (8 output tiles of 16 rows each); layer 0 one k-step, dense layers 8, views 9.
@@ -1494,7 +1496,13 @@ __global__ void __launch_bounds__(kRThreads, 1) field_r_kernel(const XFieldArgs 
     auto load_inputs = [&](uint32_t p) {
         uint32_t s = kRSamples * p + (odd ? 1u : 0u);
         if (s >= G.N) s = G.N - 1;
-        if constexpr (Net::kPosEnc) {
+        if constexpr (Net::kPosEnc && Q) {
+            // the caller's point (network coordinates): points [B,R,N,3] in a.enc; padding
+            // groups and samples read a clamped, valid one
+            const float *pv = a.enc + ((size_t)ray_index * G.N + s) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) pin[k] = __fmul_rn(pv[k], 0.5f);
+        } else if constexpr (Net::kPosEnc) {
             const float z = sample_z(G.sc, nr, fr, ray_index, s);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {

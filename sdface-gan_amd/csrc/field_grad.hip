@@ -1,5 +1,6 @@
-// field_grad.hip -- the fused ngp SDF and its exact gradient at caller-supplied points
-// (sdfr_query_ngp_grad, sdfr_render_ngp_geometry; entry points in render_api.hip):
+// field_grad.hip -- the fused SDF and its exact gradient at caller-supplied points
+// (sdfr_query_ngp_grad, sdfr_render_ngp_geometry, sdfr_query_siren_grad, sdfr_query_fc_grad;
+// entry points in render_api.hip):
 //
 //   ngp_encode_grad_kernel   points [B,M,3] -> gd: per point the 32 hash-grid features and
 //                            their 3 x 32 derivatives with respect to the grid coordinate u
@@ -8,8 +9,9 @@
 //                            its three tangents are four MFMA columns of one GEMM stream
 //
 // field_g_kernel is a template over the trunk (NgpGradNet here; SirenGradNet, the SIREN's
-// eight FiLM layers with no gather, at the end of this file).  What follows describes the
-// ngp instantiation; the SIREN section says what differs.
+// eight FiLM layers with no gather, and FcGradNet, the FC network's eight ReLU layers on
+// positional encodings, at the end of this file).  What follows describes the ngp
+// instantiation; the SIREN and FC sections say what differs.
 //
 // Gather layout (gd): [B Mp][4 kinds][32] fp32, Mp = M rounded up to 8 (one wave pass);
 // kind 0 holds the features (feature 2 level + c), kind 1 + k their derivatives d/du_k.
@@ -132,6 +134,7 @@ struct NgpGradNet {
     static constexpr int kFilmN = 3;             // pts_linears.0-2
     static constexpr uint32_t kSlices = 2 + 16 * 2;
     static constexpr bool kGather = true;        // layer-0 columns from the gather's gd
+    static constexpr bool kPosEnc = false;
     static constexpr uint32_t kFilmStride = kFilm;   // FiLM sets per face in `film`
 };
 
@@ -139,9 +142,9 @@ static_assert(RNet<NgpGradNet>::kSteps == 34 && NgpGradNet::kSlices == 34, "ngp 
 static_assert(kGradPts * 4 == 32 && kGGroup == 32, "8 points x 4 kinds per wave, 32 per pass");
 
 struct GFieldArgs {
-    const float *gd;               // ngp: [B Mp][4][32]; siren: the points [B,M,3]
+    const float *gd;               // ngp: [B Mp][4][32]; siren, fc: the points [B,M,3]
     const f4 *packed;              // NgpNet's packed weights (first 34 slices read) /
-                                   // SirenGradNet's (113 slices)
+                                   // SirenGradNet's (113 slices) / FcNet's (first 116 read)
     const float *film;             // [B][kFilmStride][2][256] (xprep_kernel)
     const float *sigma_w, *sigma_b;
     float *sdf;                    // [B,M] or null
@@ -178,6 +181,44 @@ __device__ __forceinline__ float g_act1(float zz, float g, float b, float w, boo
     const float v = tangent ? tv : sv;
     if constexpr (MODE == 2) sdfp = __fmaf_rn(v, w, sdfp);
     return v;
+}
+
+// FcGradNet's activated register: every layer is ReLU(fma(1/su, z, b)) (r_act<.., SIN =
+// false>'s arithmetic in the value lane, bit for bit).  The tangent lane takes the mask from
+// the quad's value lane: u > 0 ? (1/su) z : 0 -- at u == 0 the derivative is 0, as
+// torch.relu's backward has it.  MODE 2: the last layer (+ the sigma head's partial dot
+// product); ex as in g_act1.
+template <int MODE>
+__device__ __forceinline__ float g_relu1(float zz, float g, float b, float w, bool tangent, int ex,
+                                         float &sdfp) {
+    const float uo = __fmaf_rn(g, zz, b);
+    const float u = quad_bcast0(uo);
+    const float sv = fmaxf(u, 0.0f);
+    const float tv = u > 0.0f ? __builtin_ldexpf(__fmul_rn(g, zz), -ex) : 0.0f;
+    const float v = tangent ? tv : sv;
+    if constexpr (MODE == 2) sdfp = __fmaf_rn(v, w, sdfp);
+    return v;
+}
+
+// Element e of FcGradNet's layer-0 column `kind` at ph = p / 2.  kind 0, the value column:
+// posenc_val(ph, e), by the same operations (the phase offset 0 of a sine entry adds
+// nothing).  kind 1 + k, the tangent column d / d p_k: with arg = RN(c_i ph_k) and
+// c_i = RN32(2^i pi) as in posenc_val, + cos(arg) c_i / 2 for a sine entry and
+// - sin(arg) c_i / 2 for a cosine entry of coordinate k (c_i / 2 is exact), 0 for the
+// entries of the other coordinates; cos x = sin(x + pi / 2) and - sin x = sin(x + pi) go
+// through posenc_val's fp64 reduction to revolutions.
+__device__ __forceinline__ float posenc_col(const float (&ph)[3], uint32_t e, uint32_t kind) {
+    const uint32_t i = e / 6u, r = e - 6u * i;
+    const uint32_t c = r < 3u ? r : r - 3u;
+    const float pc = c == 0u ? ph[0] : (c == 1u ? ph[1] : ph[2]);
+    const float arg = __fmul_rn(__builtin_ldexpf(3.14159265358979323846f, (int)i), pc);
+    double u = (double)arg * 0.15915494309189533577;     // 1 / (2 pi)
+    u += kind == 0u ? (r >= 3u ? 0.25 : 0.0) : (r < 3u ? 0.25 : 0.5);
+    u -= floor(u);
+    const float s = sin_rev((float)u);
+    if (kind == 0u) return s;
+    return c + 1u == kind ? __fmul_rn(s, __builtin_ldexpf(3.14159265358979323846f, (int)i - 1))
+                          : 0.0f;
 }
 
 template <class Net>
@@ -241,9 +282,12 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
             const float *src = a.gd + ((size_t)b * a.M + m) * 3;
             const float px = src[0], py = src[1], pz = src[2];
             const bool h0 = h == 0u;
-            ld[0] = f4{h0 ? (kind == 0u ? px : (kind == 1u ? 1.0f : 0.0f)) : 0.0f,
-                       h0 ? (kind == 0u ? py : (kind == 2u ? 1.0f : 0.0f)) : 0.0f,
-                       h0 ? (kind == 0u ? pz : (kind == 3u ? 1.0f : 0.0f)) : 0.0f, 0.0f};
+            if constexpr (Net::kPosEnc)
+                ld[0] = f4{px, py, pz, 0.0f};               // (the columns are built per pass)
+            else
+                ld[0] = f4{h0 ? (kind == 0u ? px : (kind == 1u ? 1.0f : 0.0f)) : 0.0f,
+                           h0 ? (kind == 0u ? py : (kind == 2u ? 1.0f : 0.0f)) : 0.0f,
+                           h0 ? (kind == 0u ? pz : (kind == 3u ? 1.0f : 0.0f)) : 0.0f, 0.0f};
         }
     };
     load_inputs(wg);
@@ -280,6 +324,34 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
             }
             split8(u0, E[0][0], E[0][1]);
             split8(u1, E[1][0], E[1][1]);
+        } else if constexpr (Net::kPosEnc) {
+            // the 60 encodings of pin = RN(p / 2) (value column: unscaled, exactly the
+            // render's B fragments) or their derivatives d / d p_(kind - 1) (tangent
+            // columns, up to 2^9 pi / 2: scaled by 2^es into [0.5, 1) before the split);
+            // this lane half's 8 of each k-step's 16, zero past 60
+            const float pin[3] = {__fmul_rn(ld[0][0], 0.5f), __fmul_rn(ld[0][1], 0.5f),
+                                  __fmul_rn(ld[0][2], 0.5f)};
+            float v[KL0][8];
+            float m = 0.0f;
+#pragma unroll
+            for (int st = 0; st < KL0; ++st)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const uint32_t e = 16 * st + 8 * h + j;
+                    v[st][j] = e < Net::kPosIn ? posenc_col(pin, e, kind) : 0.0f;
+                    m = fmaxf(m, fabsf(v[st][j]));
+                }
+            m = fmaxf(m, __shfl_xor(m, 32));
+            if (tangent && m > 0.0f && m < 3.0e38f) {
+                const int ex = __builtin_amdgcn_frexp_expf(m);
+                es = ex < -100 ? 100 : -ex;
+            }
+#pragma unroll
+            for (int st = 0; st < KL0; ++st) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[st][j] = __builtin_ldexpf(v[st][j], es);
+                split8(v[st], E[st][0], E[st][1]);
+            }
         } else {
             // the column's 3 inputs (lane half 0; half 1 holds zeros) -> 2^es into [0.5, 1):
             // the hi / lo split is then fp32-accurate at any coordinate magnitude
@@ -320,7 +392,10 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
             const float bb = j < 4 ? as.bt0[j & 3] : as.bt1[j & 3];
             const float w = l == KH ? (j < 4 ? as.w0[j & 3] : as.w1[j & 3]) : 0.0f;
             constexpr int MODE = l == 0 ? 0 : (l == KH ? 2 : 1);
-            as.v[j] = g_act1<MODE>(o[q >> 1][8 * (q & 1) + j], g, bb, w, tangent, es, ex, sdfp);
+            if constexpr (Net::kPosEnc)
+                as.v[j] = g_relu1<MODE>(o[q >> 1][8 * (q & 1) + j], g, bb, w, tangent, ex, sdfp);
+            else
+                as.v[j] = g_act1<MODE>(o[q >> 1][8 * (q & 1) + j], g, bb, w, tangent, es, ex, sdfp);
         };
         // activation of chunk q into bn spread over a k-step's groups: film vectors read
         // beside group 0, one register beside each of groups 1-5, two beside group 6, the
@@ -359,11 +434,12 @@ __global__ void __launch_bounds__(kRThreads, 1) field_g_kernel(const GFieldArgs 
                     for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(__fmul_rn(gm[r], o[T][4 * bq + r])));
                 }
             m = fmaxf(m, __shfl_xor(m, 32));
-            const int ex = col_exp(__fmul_rn(m, 6.28318530717958647692f));
+            // (FcGradNet: |(1/su) z|, the ReLU's slope being at most 1)
+            const int ex = col_exp(Net::kPosEnc ? m : __fmul_rn(m, 6.28318530717958647692f));
             return tangent ? ex : 0;
         };
         constexpr std::integral_constant<int, 0> L0{};
-        // layer 0: K = 32 (ngp, 2 k-steps) or 3 (siren, 1)
+        // layer 0: K = 32 (ngp, 2 k-steps), 3 (siren, 1) or 60 (fc, 4)
         sfor<0, KL0>([&](auto J) {
             constexpr int j = decltype(J)::value;
             bf[0] = E[j][0];
@@ -567,11 +643,49 @@ int launch_gprep_siren(const NetPtrs &P, uint32_t B, const float *styles, char *
     return check_launch("query_siren_grad: xprep");
 }
 
+// ----------------------------------------------------------------------------
+// FC: the SDF and its gradient at caller points (sdfr_query_fc_grad)
+//
+//   xprep_kernel<FcNet>         the render's FiLM slots and packing (launch_xprep)
+//   field_g_kernel<FcGradNet>   the forward-mode kernel over x_in, pts_linears.0-6 and
+//                               sigma_linear
+//
+// FcNet is a field_r_kernel policy with the views layer packed last, so its SDF trunk is
+// the first 4 + 16 x 7 = 116 slices of the render's own packing, as ngp's is the first 34
+// of its: no packing of its own.  Layer 0's columns are built in the kernel (posenc_col):
+// the value column holds the render's 60 encodings unscaled, so with the same slices in
+// the same k-step order the value lanes repeat the query's arithmetic and `sdf` is the
+// query's bit for bit; tangent column k holds the encodings' derivatives d / d p_k, up to
+// 2^9 pi / 2, scaled by a power of two before the split.  Every layer is ReLU: the tangent
+// lane passes (1/su) z where the quad's value lane has u > 0 (g_relu1).  The per-layer
+// power-of-two rescale of the tangent columns is the other trunks'; it also carries
+// gradients far below fp16's range (a trunk whose late layers are nearly dead).
+// ----------------------------------------------------------------------------
+struct FcGradNet {
+    static constexpr bool kPosEnc = true;
+    static constexpr int kL0 = 4;                // 60 encodings (+ 4 zero pad)
+    static constexpr int kHidden = 7;
+    static constexpr int kViewSteps = 0;
+    static constexpr bool kFieldR = true;
+    static constexpr int kFilmN = 8;             // x_in, pts_linears.0-6
+    static constexpr uint32_t kSlices = 4 + 16 * 7;
+    static constexpr bool kGather = false;       // layer-0 columns from the point itself
+    static constexpr uint32_t kFilmStride = kFcFilm;   // the render's sets per face
+    static constexpr uint32_t kPosIn = FcNet::kPosIn;
+};
+static_assert(RNet<FcGradNet>::kSteps == 116 && FcGradNet::kSlices == 116 &&
+                  FcGradNet::kL0 == FcNet::kL0 && FcGradNet::kHidden == FcNet::kHidden &&
+                  rslice_base<FcNet>(FcNet::kLayers - 1) == 116,
+              "fc trunk: the render's slices ahead of its views layer");
+
 int launch_gfield(int net, const NetPtrs &P, const char *xws, const float *film, const float *in,
                   float *sdf, float *grad, uint32_t B, uint32_t M, float bound, hipStream_t st) {
     if (net == kNetNgp)
         return launch_gfield_net<NgpGradNet>(P, xws, film, in, sdf, grad, B, M, bound,
                                              "query_ngp_grad: field (f16x3)", st);
+    if (net == kNetFc)
+        return launch_gfield_net<FcGradNet>(P, xws, film, in, sdf, grad, B, M, 0.0f,
+                                            "query_fc_grad: field (f16x3)", st);
     return launch_gfield_net<SirenGradNet>(P, xws, film, in, sdf, grad, B, M, 0.0f,
                                            "query_siren_grad: field (f16x3)", st);
 }

@@ -1,6 +1,6 @@
 // render_api.hip -- the C entry points of the fused renderer (include/sdfr.h): the render of
 // the three networks (ngp, SIREN, FC), the field query and the SDF gradient at caller points
-// (ngp, SIREN), the ngp geometry render, the surface render (ngp, SIREN), and their packing
+// (ngp, SIREN, FC), the ngp geometry render, the surface render (ngp, SIREN), and their packing
 // and workspace-size calls.
 //
 // Host code only.  An entry point checks its arguments, lays out its workspace and enqueues
@@ -171,6 +171,19 @@ FilmWs siren_grad_ws(uint32_t B, uint32_t M) {
     const uint64_t P = (uint64_t)B * (((uint64_t)M + kGradPts - 1) / kGradPts * kGradPts);
     if (P == 0 || P >= kSirenMaxPoints) return FilmWs{};
     return film_ws(B, kSirenGradFilm, siren_grad_pack_bytes(), 0);
+}
+
+// FC point calls (query, gradient): film [B][9][2][256] | the render's weight region -- the
+// FC render's workspace without segment partials.  The kernels index the points as the
+// SIREN's do, so the padded counts and their limit are the SIREN calls' (total 0: too many).
+FilmWs fc_query_ws(uint32_t B, uint32_t R, uint32_t N) {
+    if (siren_query_padded(B, R, N) == 0) return FilmWs{};
+    return film_ws(B, kFcFilm, f16x3_ws_bytes(kNetFc), 0);
+}
+FilmWs fc_grad_ws(uint32_t B, uint32_t M) {
+    const uint64_t P = (uint64_t)B * (((uint64_t)M + kGradPts - 1) / kGradPts * kGradPts);
+    if (P == 0 || P >= kSirenMaxPoints) return FilmWs{};
+    return film_ws(B, kFcFilm, f16x3_ws_bytes(kNetFc), 0);
 }
 
 // surface render (net: kNetNgp or kNetSiren).  With M = H W rays per face, Mp = M rounded up
@@ -898,6 +911,57 @@ int sdfr_query_siren_grad(const sdfr_siren_weights *w, const sdfr_siren_grad_arg
     if ((rc = launch_gprep_siren(P, a->B, a->styles, xws, film, !a->prepacked, st))) return rc;
     return launch_gfield(kNetSiren, P, xws, film, a->points, a->sdf, a->grad, a->B, a->M, 0.0f,
                          st);
+}
+
+// ----------------------------------------------------------------------------
+// FC field query and SDF gradient at caller points: the FC render's FiLM prep and packing
+// (launch_xprep), then field_r_kernel in query mode (field_fc_query.hip) or the forward-mode
+// kernel on the first 116 slices of the same packing (field_grad.hip)
+// ----------------------------------------------------------------------------
+size_t sdfr_query_fc_workspace_bytes(uint32_t B, uint32_t R, uint32_t N) {
+    return fc_query_ws(B, R, N).total;
+}
+
+int sdfr_query_fc_forward(const sdfr_fc_weights *w, const sdfr_fc_query_args *a, void *stream) {
+    const char *who = "query_fc";
+    int rc = check_query_args(w, a, who);
+    if (rc || (rc = check_fc_weights(w, who))) return rc;
+    const FilmWs l = fc_query_ws(a->B, a->R, a->N);
+    if (l.total == 0)
+        return err(who, SDFR_EINVAL, "too many samples per call (split the points)");
+    if (a->workspace_bytes < l.total) return err(who, SDFR_EINVAL, "workspace too small");
+
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(a->workspace);
+    float *film = reinterpret_cast<float *>(ws);
+    char *xws = weight_region(a->prepacked, ws + l.x);
+    const NetPtrs P = fc_ptrs(w);
+    const GeomArgs g = query_geom(a->B, a->R, a->N, siren_query_padded(a->B, a->R, a->N),
+                                  a->dirs, 0.0f);
+    if ((rc = launch_xprep(kNetFc, P, a->B, a->styles, xws, film, !a->prepacked, st))) return rc;
+    return launch_qfield_fc(P, g, a->points, xws, film, a->sdf, a->rgb, st);
+}
+
+size_t sdfr_query_fc_grad_workspace_bytes(uint32_t B, uint32_t M) {
+    return fc_grad_ws(B, M).total;
+}
+
+int sdfr_query_fc_grad(const sdfr_fc_weights *w, const sdfr_fc_grad_args *a, void *stream) {
+    const char *who = "query_fc_grad";
+    int rc = check_grad_args(w, a, who);
+    if (rc || (rc = check_fc_weights(w, who))) return rc;
+    const FilmWs l = fc_grad_ws(a->B, a->M);
+    if (l.total == 0)
+        return err(who, SDFR_EINVAL, "too many points per call (split the points)");
+    if (a->workspace_bytes < l.total) return err(who, SDFR_EINVAL, "workspace too small");
+
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(a->workspace);
+    float *film = reinterpret_cast<float *>(ws);
+    char *xws = weight_region(a->prepacked, ws + l.x);
+    const NetPtrs P = fc_ptrs(w);
+    if ((rc = launch_xprep(kNetFc, P, a->B, a->styles, xws, film, !a->prepacked, st))) return rc;
+    return launch_gfield(kNetFc, P, xws, film, a->points, a->sdf, a->grad, a->B, a->M, 0.0f, st);
 }
 
 // ----------------------------------------------------------------------------

@@ -67,6 +67,11 @@ int launch_query_geom(const float *points, f4 *gu, const GeomArgs &g, hipStream_
 int launch_qfield(int net, const NetPtrs &P, const GeomArgs &g, const float *in, const char *xws,
                   const float *film, float *sdf, float *rgb, hipStream_t st);
 
+// ---- field_fc_query.hip: the FC field at caller points ------------------------------
+// g as for launch_qfield; field_r_kernel on the points [B,R,N,3] themselves
+int launch_qfield_fc(const NetPtrs &P, const GeomArgs &g, const float *points, const char *xws,
+                     const float *film, float *sdf, float *rgb, hipStream_t st);
+
 // ---- field_grad.hip: SDF and gradient at caller points ------------------------------
 constexpr uint32_t kGradPts = 8;             // points per wave pass: the padding unit of M
 constexpr uint32_t kGradPointBytes = 4 * kFeatIn * sizeof(float);   // gd per padded point
@@ -74,7 +79,8 @@ constexpr uint32_t kGradPointBytes = 4 * kFeatIn * sizeof(float);   // gd per pa
 int launch_grad_gather(const sdfr_ngp_weights *w, const float *points, float *gd, uint32_t B,
                        uint32_t M, uint32_t Mp, hipStream_t st);
 // the forward-mode field kernel (net: kNetNgp on the gather's gd with the grid's `bound`,
-// kNetSiren on the points [B,M,3] themselves); sdf [B,M] or null, grad [B,M,3]
+// kNetSiren and kNetFc on the points [B,M,3] themselves; kNetFc on the render's xws and
+// film of launch_xprep); sdf [B,M] or null, grad [B,M,3]
 int launch_gfield(int net, const NetPtrs &P, const char *xws, const float *film, const float *in,
                   float *sdf, float *grad, uint32_t B, uint32_t M, float bound, hipStream_t st);
 // SIREN: the SDF trunk in field_r_kernel's packing (siren_grad_pack_bytes(): packed slices |

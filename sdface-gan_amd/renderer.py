@@ -758,11 +758,13 @@ class VolumeFeatureRenderer(nn.Module):
 
     def _query_fused_ok(self, points, styles):
         """The rule of ``_fused_ok`` for a point query (the fused query and gradient exist
-        for the ngp and SIREN networks on the f16x3 field kernel; FC stays on the module)."""
+        for the three networks on the f16x3 field kernel; SIREN and FC in the shape their
+        kernels are built for: D = 8, W = 256)."""
         kind = self._net_kind()
-        if kind not in (0, 1) or self.field_precision != "f16x3":
+        if kind is None or self.field_precision != "f16x3":
             return False
-        if kind == 1 and (self.network.D != 8 or len(self.network.pts_linears) != 8):
+        if kind and (self.network.D != 8 or
+                     len(self.network.pts_linears) != (8 if kind == 1 else 7)):
             return False
         return self._fused_inputs_ok(points, styles, no_grad_on=(points,))
 
@@ -777,21 +779,22 @@ class VolumeFeatureRenderer(nn.Module):
         not normalised here): ``[B,3]`` one per face, ``[B,M,3]`` one per point, or
         ``None`` with ``return_rgb=False`` (zeros are passed).
 
-        For an ngp or SIREN network, CUDA tensors, ``field_precision == 'f16x3'`` and no
-        grad needed this runs ``sdfr_query_ngp_forward`` / ``sdfr_query_siren_forward``:
+        For CUDA tensors, ``field_precision == 'f16x3'`` and no grad needed this runs
+        ``sdfr_query_ngp_forward`` / ``sdfr_query_siren_forward`` / ``sdfr_query_fc_forward``:
         the render's split-fp16 field kernel (for ngp behind the render's hash-grid
         gather) on the given points, so a point the render samples gets the render's SDF
         bit for bit.  Per-face (or no) directions run in groups of N = 32 points (M
         padded, the padding trimmed); per-point directions run as M groups of N = 1,
-        which idles the kernel's other sample lanes (ngp takes 2 points of a group per
-        pass: half rate; SIREN takes 4: quarter rate).  Calls are chunked over groups
+        which idles the kernel's other sample lanes (ngp and FC take 2 points of a group
+        per pass: half rate; SIREN takes 4: quarter rate).  Calls are chunked over groups
         (``chunk_groups``, default ``QUERY_CHUNK_POINTS`` / N) to bound the workspace;
         chunking does not change a bit of the result.  The SIREN kernel splits each
         coordinate into fp16 hi + lo parts unscaled, as its render does: coordinates
         must stay below fp16's 65504, and the accuracy tests cover |coordinate| <= 64,
-        the supported range (the render's samples stay below 1.3).  Otherwise (FC, CPU
-        tensors, the fp32 field, a call under grad) it runs
-        ``self.network(cat([points, dirs]), styles)``, the autograd path, and slices it.
+        the supported range (the render's samples stay below 1.3).  Otherwise (CPU
+        tensors, the fp32 field, a call under grad, a SIREN or FC network of another
+        depth or width) it runs ``self.network(cat([points, dirs]), styles)``, the autograd
+        path, and slices it.
         """
         if points.dim() != 3 or points.shape[-1] != 3:
             raise ValueError(f"query: points must be [B,M,3], got {tuple(points.shape)}")
@@ -822,7 +825,7 @@ class VolumeFeatureRenderer(nn.Module):
         return sdf, (rgb.reshape(B, R * N, 3)[:, :M] if return_rgb else None)
 
     def _fused_query(self, points, dirs, styles, return_rgb=True, chunk_groups=None):
-        """``sdfr_query_ngp_forward`` / ``sdfr_query_siren_forward`` on grouped points:
+        """``sdfr_query_{ngp,siren,fc}_forward`` on grouped points:
         ``points`` [B,R,N,3], ``dirs`` [B,R,3] (one per group) -> (sdf [B,R,N],
         rgb [B,R,N,3] | None), in calls of at most ``chunk_groups`` groups per face."""
         self._fused_check_params()
@@ -838,9 +841,11 @@ class VolumeFeatureRenderer(nn.Module):
         kind = self._net_kind()
         prepacked = self._prepacked(kind, pts)
         w = self._weight_struct(kind)
-        Args = (_lib.NgpQueryArgs, _lib.SirenQueryArgs)[kind]
-        name = ("sdfr_query_ngp_forward", "sdfr_query_siren_forward")[kind]
-        ws_bytes = (L.sdfr_query_ngp_workspace_bytes, L.sdfr_query_siren_workspace_bytes)[kind]
+        Args = (_lib.NgpQueryArgs, _lib.SirenQueryArgs, _lib.FcQueryArgs)[kind]
+        name = ("sdfr_query_ngp_forward", "sdfr_query_siren_forward",
+                "sdfr_query_fc_forward")[kind]
+        ws_bytes = (L.sdfr_query_ngp_workspace_bytes, L.sdfr_query_siren_workspace_bytes,
+                    L.sdfr_query_fc_workspace_bytes)[kind]
         fn = getattr(L, name)
 
         def call(r, ins, outs, ws):
@@ -900,13 +905,17 @@ class VolumeFeatureRenderer(nn.Module):
         trilinear field, ``sdf`` bit-identical to ``query``'s) or ``sdfr_query_siren_grad``
         (SIREN: the same forward-mode kernel over the eight FiLM layers with the point and
         the three unit vectors as layer 0's columns, on a packing of the trunk of its own;
-        ``sdf`` equals ``query``'s up to fp32 rounding, the accumulation order differs).
+        ``sdf`` equals ``query``'s up to fp32 rounding, the accumulation order differs) or
+        ``sdfr_query_fc_grad`` (FC: the same kernel over x_in and the seven ReLU layers on
+        the render's own packing, layer 0's columns being the positional encodings and
+        their derivatives; a tangent passes a ReLU where the value's pre-activation is
+        > 0, as ``torch.relu``'s backward has it; ``sdf`` bit-identical to ``query``'s).
         No autograd graph is built.  Calls
         are chunked over points (``chunk_points`` per face, rounded down to the kernel's
         workgroup pass of 32 points; default ``GRADIENT_CHUNK_POINTS`` / B) to bound the
-        workspace; chunking does not change a bit of the result.  Otherwise (FC,
-        CPU tensors, the fp32 field, grad mode with a tensor or parameter that requires
-        grad) it is ``torch.autograd.grad(sdf.sum(), points)``
+        workspace; chunking does not change a bit of the result.  Otherwise (CPU
+        tensors, the fp32 field, grad mode with a tensor or parameter that requires grad)
+        it is ``torch.autograd.grad(sdf.sum(), points)``
         through ``self.network`` with zero view directions, on a detached copy of the
         points with grad enabled locally -- so it also works under ``no_grad``, and the
         caller's ``points`` are left alone.  Either way the result carries no autograd
@@ -940,7 +949,7 @@ class VolumeFeatureRenderer(nn.Module):
         return sdf, (_unit(grad, -1) if normalize else grad)
 
     def _fused_gradient(self, points, styles, chunk_points=None, encode_only=False):
-        """``sdfr_query_ngp_grad`` / ``sdfr_query_siren_grad`` on ``points`` [B,M,3] in
+        """``sdfr_query_{ngp,siren,fc}_grad`` on ``points`` [B,M,3] in
         calls of at most ``chunk_points`` points per face."""
         self._fused_check_params()
         dev = points.device
@@ -956,13 +965,15 @@ class VolumeFeatureRenderer(nn.Module):
             chunk_points = max(chunk_points, M)      # one call: its workspace is the result
         L = _lib.lib()
         kind = self._net_kind()
-        # (SIREN: the gradient kernel's own packing of the trunk, cached beside the render's)
+        # (SIREN: the gradient kernel's own packing of the trunk, cached beside the render's;
+        # ngp and FC: the render's packing)
         prepacked = self._prepacked(kind, pts, grad=kind == 1)
         w = self._weight_struct(kind)
-        Args = (_lib.NgpGradArgs, _lib.SirenGradArgs)[kind]
-        name = ("sdfr_query_ngp_grad", "sdfr_query_siren_grad")[kind]
+        Args = (_lib.NgpGradArgs, _lib.SirenGradArgs, _lib.FcGradArgs)[kind]
+        name = ("sdfr_query_ngp_grad", "sdfr_query_siren_grad", "sdfr_query_fc_grad")[kind]
         ws_bytes = (L.sdfr_query_ngp_grad_workspace_bytes,
-                    L.sdfr_query_siren_grad_workspace_bytes)[kind]
+                    L.sdfr_query_siren_grad_workspace_bytes,
+                    L.sdfr_query_fc_grad_workspace_bytes)[kind]
         fn = getattr(L, name)
 
         def call(m, ins, outs, ws):
@@ -1161,7 +1172,7 @@ class VolumeFeatureRenderer(nn.Module):
         miss every float map is 0.  The sampling flags are the renderer's; ``t_rand`` is
         drawn as in ``forward`` when ``perturb > 0`` and none is given.
 
-        Under the rule of ``query``'s fused path (ngp and SIREN) this runs
+        For an ngp or SIREN network under the rule of ``query``'s fused path this runs
         ``sdfr_render_ngp_surface`` / ``sdfr_render_siren_surface`` in calls of at most
         ``chunk_points`` samples (default ``SURFACE_CHUNK_POINTS``) over faces and bands of
         whole image rows; rays are independent, so chunking does not change a bit.
@@ -1179,8 +1190,9 @@ class VolumeFeatureRenderer(nn.Module):
         refine_steps = int(refine_steps)
         if not 0 <= refine_steps <= 32:
             raise ValueError(f"render_surface: refine_steps must be 0..32, got {refine_steps}")
-        path = (self._fused_surface if self._query_fused_ok(cam_poses, styles)
-                else self._module_surface)
+        # (the fused surface render is ngp's and SIREN's; FC has the fused point calls only)
+        fused = self._net_kind() in (0, 1) and self._query_fused_ok(cam_poses, styles)
+        path = self._fused_surface if fused else self._module_surface
         out = path(cam_poses, focal, near, far, styles, t_rand, refine_steps, want, chunk_points)
         return Surface(**{k: out.get(k) for k in self.SURFACE_FIELDS})
 
