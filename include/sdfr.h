@@ -997,6 +997,76 @@ int sdfr_mc_emit(const float *vol, uint32_t n0, uint32_t n1, uint32_t n2, int64_
                  int64_t s1, int64_t s2, float level, const void *ws, size_t ws_bytes,
                  float *verts, int32_t *faces, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Sparse marching cubes: narrow-band SDF bricks (csrc/mesh_sparse.hip).
+ *
+ * Grid and bricks.  The grid has res points per axis, res a multiple of 8; a point
+ * has index (ix, iy, iz), a cell its low corner at ix, iy, iz <= res - 2.  A brick
+ * is 8 x 8 x 8 points; nb = res / 8 bricks per axis (1 <= nb <= 256), brick
+ * (bx, by, bz) has linear index q = (bx nb + by) nb + bz.  A cell belongs to the
+ * brick of its low corner, so the cells of brick K read points of K + {0,1}^3.
+ * Storage: values [n, 8, 8, 8] fp32 (local lx, ly, lz; lz fastest), a slot table
+ * slots [nb^3] int32 (slot, or -1) and surface [nb^3] uint8 (the bricks whose
+ * cells are triangulated).  A point is inside when v < level, as in the dense code.
+ *
+ * Layout.  A brick is needed when it lies in K + {0,1}^3 (clipped to the grid) of
+ * some surface brick K.  Needed bricks without a slot get the slots n_prev,
+ * n_prev + 1, ... in ascending q; existing slots never move.
+ *
+ * Mesh.  The cells of surface bricks are triangulated with mc_table.h; a vertex
+ * sits on each crossed grid edge by the dense code's arithmetic (low end +
+ * fdiv(fsub(level, va), fsub(vb, va))), in global index coordinates, and only on
+ * an edge that an emitted triangle references (an edge of a surface brick's
+ * cell): no unreferenced vertices.  Vertices are shared between cells and across
+ * brick borders as in the dense mesh, which the result equals, as a set of
+ * triangles, on the cells of surface bricks.  Order is a pure function of slots
+ * and values: slot-major; within a brick vertices axis-major then local point
+ * order, triangles in local cell order then table order.
+ *
+ * Leaks.  For a cell of surface brick K and one of its faces whose cell across
+ * exists and lies in a brick K' that is not surface: if the face's four corners
+ * are not all on the same side of level, grow[K'] = 1.  Growth (the caller's
+ * loop): surface |= grow, layout, evaluate the new slots, count again, until grow
+ * is all zero; the final surface set is the closure of the first one under leaks.
+ *
+ *   sdfr_brick_layout:  dilates surface to the needed bricks and assigns the new
+ *                       slots (ws: sdfr_brick_layout_workspace_bytes(nb)); writes
+ *                       the number of slots now in use to HOST memory *n_total
+ *                       (synchronises stream).  slots starts as all -1, n_prev 0.
+ *   sdfr_brick_points:  points [(slot1 - slot0) 512, 3] of the bricks with a slot in
+ *                       [slot0, slot1), brick-major in slot order: point
+ *                       (ix, iy, iz) is (ax[ix], ay[iy], az[iz]), ax / ay / az [res]
+ *                       fp32 tables (entries are copied, nothing is computed).
+ *   sdfr_mc_sparse_count: classify + scan into ws
+ *                       (sdfr_mc_sparse_workspace_bytes(n_bricks): 16 bytes per
+ *                       stored point + 4 per brick + the scan's block sums);
+ *                       n_bricks = the layout's n_total, every slot's values
+ *                       filled.  grow [nb^3] uint8 or NULL: cleared, then set to 1
+ *                       per the leak rule with plain stores.  counts[0] = vertices,
+ *                       counts[1] = triangles to HOST memory (synchronises stream).
+ *   sdfr_mc_sparse_emit: same arguments and ws (after the count): verts [V,3] fp32,
+ *                       faces [F,3] int32 (vertex ids), device.
+ *
+ * SDFR_EINVAL before any launch for null pointers (grow excepted), nb == 0 or
+ * nb > 256, n_bricks == 0, 4 * 512 n_bricks + 1 >= 2^32 (the size function
+ * returns 0 for such a count), a short workspace, slot0 >= slot1.  Table entries
+ * are bounds-checked on the device: a slot outside [0, n_bricks) reads as NaN.
+ * Everything but the two host reads is asynchronous on stream; nothing allocates.
+ * ------------------------------------------------------------------------- */
+size_t sdfr_brick_layout_workspace_bytes(uint32_t nb);
+int sdfr_brick_layout(const uint8_t *surface, uint32_t nb, int32_t *slots, uint32_t n_prev,
+                      void *ws, size_t ws_bytes, uint32_t *n_total, void *stream);
+int sdfr_brick_points(const int32_t *slots, uint32_t nb, uint32_t slot0, uint32_t slot1,
+                      const float *ax, const float *ay, const float *az, float *points,
+                      void *stream);
+size_t sdfr_mc_sparse_workspace_bytes(uint32_t n_bricks);
+int sdfr_mc_sparse_count(const float *values, const int32_t *slots, const uint8_t *surface,
+                         uint32_t nb, uint32_t n_bricks, float level, void *ws, size_t ws_bytes,
+                         uint8_t *grow, uint32_t *counts, void *stream);
+int sdfr_mc_sparse_emit(const float *values, const int32_t *slots, const uint8_t *surface,
+                        uint32_t nb, uint32_t n_bricks, float level, const void *ws,
+                        size_t ws_bytes, float *verts, int32_t *faces, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,10 @@ eikonal check); VolumeFeatureRenderer.render_geometry / Generator.render_geometr
 fused: sdfr_render_ngp_geometry); VolumeFeatureRenderer.render_surface /
 Generator.render_surface -> Surface (per ray the SDF's first zero crossing, refined by
 bisection, with the unit normal and the field's colour there, fused:
-sdfr_render_ngp_surface / sdfr_render_siren_surface), shade_surface (a lit view of it).
+sdfr_render_ngp_surface / sdfr_render_siren_surface), shade_surface (a lit view of it);
+extract_mesh_sparse / Generator.extract_mesh (the field's mesh at up to 1024^3 from
+narrow-band 8^3 bricks, grown along the surface: csrc/mesh_sparse.hip), sparse_extract (the
+generic driver), SparseVolume, cube_axis.
   SDFOptions, vol_render_opt                            (sdf_utils.py:447, training_utils.py:144)
 Beyond the reference: GraphedGenerator (HIP-graph replay of the inference forward).
 """
@@ -33,9 +36,10 @@ from .generator import (Blur, Decoder, EqualLinear, FusedLeakyReLU, Generator,  
                         MappingLinear, ModulatedConv2d, NoiseInjection, PixelNorm, StyledConv,
                         ToRGB, Upsample, fused_leaky_relu, make_kernel, upfirdn2d)
 from .graphs import GraphedGenerator  # noqa: F401
-from .mesh import (Mesh, align_volume, color_mesh, cube_points,  # noqa: F401
-                   eikonal_residual, extract_mesh_with_marching_cubes, marching_cubes,
-                   normal_mesh, sdf_cube, shade_surface, world_to_network, xyz2mesh)
+from .mesh import (Mesh, SparseVolume, align_volume, color_mesh, cube_axis,  # noqa: F401
+                   cube_points, eikonal_residual, extract_mesh_sparse,
+                   extract_mesh_with_marching_cubes, marching_cubes, normal_mesh, sdf_cube,
+                   shade_surface, sparse_extract, world_to_network, xyz2mesh)
 from .options import AttrDict, SDFOptions, vol_render_opt  # noqa: F401
 from . import training  # noqa: F401  (stage-2 DDP trainer, Discriminator, losses)
 from .renderer import (FCGenerator, FiLMSiren, Geometry, LinearLayer,  # noqa: F401

@@ -58,6 +58,8 @@ EXPORTS = (
     "sdfr_conv3x3_f16x3_act", "sdfr_conv_act_ws_bytes", "sdfr_rgb_finish",
     "sdfr_conv_t_act", "sdfr_conv_t_act_supported",
     "sdfr_mc_workspace_bytes", "sdfr_mc_count", "sdfr_mc_emit",
+    "sdfr_brick_layout_workspace_bytes", "sdfr_brick_layout", "sdfr_brick_points",
+    "sdfr_mc_sparse_workspace_bytes", "sdfr_mc_sparse_count", "sdfr_mc_sparse_emit",
     "sdfr_linear_pack_bytes", "sdfr_linear_pack", "sdfr_linear_f16x3",
     "sdfr_linear_wgrad_ws_bytes", "sdfr_linear_wgrad_f16x3",
     "sdfr_film_linear_f16x3", "sdfr_film_backward_ws_bytes", "sdfr_film_backward",
@@ -358,6 +360,17 @@ def lib():
                                 ctypes.c_size_t, ctypes.POINTER(_u32), _vp]
     L.sdfr_mc_emit.argtypes = [_vp, _u32, _u32, _u32, _i64, _i64, _i64, _f32, _vp,
                                ctypes.c_size_t, _vp, _vp, _vp]
+    L.sdfr_brick_layout_workspace_bytes.argtypes = [_u32]
+    L.sdfr_brick_layout_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_brick_layout.argtypes = [_vp, _u32, _vp, _u32, _vp, ctypes.c_size_t,
+                                    ctypes.POINTER(_u32), _vp]
+    L.sdfr_brick_points.argtypes = [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]
+    L.sdfr_mc_sparse_workspace_bytes.argtypes = [_u32]
+    L.sdfr_mc_sparse_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_mc_sparse_count.argtypes = [_vp, _vp, _vp, _u32, _u32, _f32, _vp, ctypes.c_size_t,
+                                       _vp, ctypes.POINTER(_u32), _vp]
+    L.sdfr_mc_sparse_emit.argtypes = [_vp, _vp, _vp, _u32, _u32, _f32, _vp, ctypes.c_size_t,
+                                      _vp, _vp, _vp]
     L.sdfr_rgb_finish.argtypes = [_vp, _vp, _u32, _vp, _vp, ctypes.POINTER(_f32), _u32, _u32,
                                   _u32, _vp]
     L.sdfr_linear_pack_bytes.argtypes = [_u32, _u32]

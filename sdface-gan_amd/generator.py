@@ -878,6 +878,15 @@ class Generator(nn.Module):
         return self.renderer.query_gradient(points, lat0, normalize=normalize,
                                             chunk_points=chunk_points)
 
+    def extract_mesh(self, styles, res=512, truncation=1, truncation_latent=None,
+                     input_is_latent=False, **kw):
+        """The mesh of the face of ``styles`` (one face) from narrow-band bricks: the
+        mapping network and truncation of ``query_field``, then ``mesh.extract_mesh_sparse``
+        (``kw``: level, lipschitz, grow, return_volume) -> ``Mesh``."""
+        from .mesh import extract_mesh_sparse
+        lat0 = self._renderer_latent(styles, truncation, truncation_latent, input_is_latent)
+        return extract_mesh_sparse(self.renderer, lat0, res=res, **kw)
+
     def render_geometry(self, styles, cam_poses, focals, near, far, truncation=1,
                         truncation_latent=None, input_is_latent=False, **kw):
         """The geometry of the faces of ``styles`` seen from ``cam_poses``: the mapping
