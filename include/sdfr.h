@@ -1067,6 +1067,88 @@ int sdfr_mc_sparse_emit(const float *values, const int32_t *slots, const uint8_t
                         uint32_t nb, uint32_t n_bricks, float level, const void *ws,
                         size_t ws_bytes, float *verts, int32_t *faces, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Mesh rasteriser (added to ABI 15 without a version step: additive; csrc/raster.hip):
+ * B views of one indexed mesh with the render's own pinhole camera, the nearest triangle
+ * per pixel, deterministic.  Where the reference rasterises with pytorch3d
+ * (sdf_model.py:754-782, sdf_utils.py:209-331).  Every floating-point step below is one
+ * rounded fp32 operation (fadd / fsub / fmul / fdiv = round to nearest even, nothing
+ * contracted), every integer step exact in int64, so a NumPy float32 / int64 transcription
+ * (tests/raster_ref.py) gives the same bits.
+ *
+ * Vertex.  cam [B,3,4] is camera-to-world (rotation R = cam[:, :, :3], origin t =
+ * cam[:, :, 3]).  d_m = fsub(v_m, t_m); the camera-frame point
+ *   q_k = fadd(fadd(fmul(d_0, R[0][k]), fmul(d_1, R[1][k])), fmul(d_2, R[2][k]));
+ * the depth z = -q_2; the screen position
+ *   x = fadd(cx, fdiv(fmul(focal, q_0), z)),   y = fsub(cy, fdiv(fmul(focal, q_1), z)).
+ * This inverts the render's ray generation: the pixel centre (i + 0.5, j + 0.5) with
+ * cx = cy = res / 2 is the ray of pixel (column i, row j).
+ * Fixed point, twelve subpixel bits: X = rint(fmul(x, 4096)), Y = rint(fmul(y, 4096))
+ * (round half to even); rz = fdiv(1, z).  A vertex is unusable when z is not finite,
+ * !(z > znear), or X or Y is not finite or has magnitude >= 2^30.
+ *
+ * Triangle (a, b, c), id = its row in faces.  Culled whole when an index is outside
+ * [0, V), a vertex is unusable, or the doubled area
+ *   A = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa)
+ * is 0.  No back-face culling.
+ *
+ * Coverage of pixel (i, j), centre (Px, Py) = (4096 i + 2048, 4096 j + 2048):
+ *   w1 = (Px - Xa)(Yc - Ya) - (Py - Ya)(Xc - Xa)
+ *   w2 = (Xb - Xa)(Py - Ya) - (Yb - Ya)(Px - Xa)
+ *   w0 = A - w1 - w2,
+ * all three negated when A < 0; covered when all are >= 0 (edges inclusive: a pixel centre
+ * on an edge two triangles share belongs to both, and the resolve decides).
+ *
+ * Depth and barycentrics.  l_i = fdiv(float(w_i), float(|A|)) (int64 -> fp32, nearest
+ * even); iz = fadd(fadd(fmul(l0, rz_a), fmul(l1, rz_b)), fmul(l2, rz_c));
+ * depth = fdiv(1, iz); the perspective-correct bary_i = fmul(fmul(l_i, rz_i), depth).
+ * depth is the camera depth (the ray parameter of the render's unnormalised direction,
+ * whose camera z is -1).  A depth that is not a positive finite number covers nothing.
+ *
+ * Resolve.  Each pixel keeps the minimum of the key (bits(depth) << 32) | id over the
+ * triangles that cover it: the nearest one, the smallest id among equal depths.  The
+ * minimum does not depend on the order in which triangles arrive, so the result is
+ * reproducible bit for bit.
+ *
+ * Outputs (each may be NULL, one is required): face_idx [B,H,W] int32 (-1: uncovered),
+ * depth [B,H,W], bary [B,H,W,3]; an uncovered pixel's depth and bary are 0.
+ * Workspace, regions in order, each rounded up to 256 bytes: projected vertices
+ * [B V] (X, Y, z, rz) 16 B | keys [B H W] 8 B | a counter (256 B) | the list of the
+ * triangles whose clamped bounding box exceeds 64 pixels [B F] 8 B.  The size function
+ * returns 0 for zero sizes, H or W above 16384, and B V, B F or B H W at or above 2^31.
+ * SDFR_EINVAL before any launch for null arguments or required pointers, zero sizes,
+ * every output null, znear negative or not finite, sizes the size function rejects, or a
+ * workspace below its value.  Asynchronous on `stream`; allocates nothing; nothing is
+ * read back.
+ *
+ * sdfr_mesh_interpolate: out[b, c, j, i] for the C channels of a per-vertex attribute
+ * attr [V, C]: with (i0, i1, i2) the face face_idx[b, j, i] names,
+ *   fadd(fadd(fmul(bary0, attr[i0, c]), fmul(bary1, attr[i1, c])), fmul(bary2, attr[i2, c]));
+ * where face_idx is outside [0, F) (uncovered) or the face has an index outside [0, V):
+ * background[b or 0, c, j, i] when a background is given ([background_batch, C, H, W],
+ * background_batch 1 or B), else fill.  SDFR_EINVAL for null pointers, zero sizes, a
+ * background_batch that is neither 1 nor B, or B C H W at or above 2^31.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfr_raster_args {
+    uint32_t B, H, W, V, F;           /* views, image rows, cols, vertices, triangles       */
+    const float *vertices;            /* [V,3]                                              */
+    const int32_t *faces;             /* [F,3]                                              */
+    const float *cam;                 /* [B,3,4] camera-to-world                            */
+    const float *focal;               /* [B] (device)                                       */
+    float cx, cy, znear;
+    int32_t *face_idx;                /* [B,H,W], optional                                  */
+    float *depth;                     /* [B,H,W], optional                                  */
+    float *bary;                      /* [B,H,W,3], optional                                */
+    void *workspace; size_t workspace_bytes;
+} sdfr_raster_args;
+size_t sdfr_mesh_raster_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t V,
+                                        uint32_t F);
+int sdfr_mesh_raster(const sdfr_raster_args *a, void *stream);
+int sdfr_mesh_interpolate(const float *attr, uint32_t V, uint32_t C, const int32_t *faces,
+                          uint32_t F, const int32_t *face_idx, const float *bary, uint32_t B,
+                          uint32_t H, uint32_t W, const float *background,
+                          uint32_t background_batch, float fill, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,12 @@ bisection, with the unit normal and the field's colour there, fused:
 sdfr_render_ngp_surface / sdfr_render_siren_surface), shade_surface (a lit view of it);
 extract_mesh_sparse / Generator.extract_mesh (the field's mesh at up to 1024^3 from
 narrow-band 8^3 bricks, grown along the surface: csrc/mesh_sparse.hip), sparse_extract (the
-generic driver), SparseVolume, cube_axis.
+generic driver), SparseVolume, cube_axis; rasterize_mesh -> Raster (B views of a Mesh, nearest
+triangle per pixel with depth and perspective-correct barycentrics, deterministic:
+csrc/raster.hip, sdfr_mesh_raster), interpolate_vertex_attributes (sdfr_mesh_interpolate),
+render_mesh (the Surface of a mesh), load_obj, subdivide_mesh; with them
+Generator.forward(project_noise=True, mesh_path=...) (NoiseInjection.project_noise,
+Decoder.reset_projected_noise), where the reference needs pytorch3d.
   SDFOptions, vol_render_opt                            (sdf_utils.py:447, training_utils.py:144)
 Beyond the reference: GraphedGenerator (HIP-graph replay of the inference forward).
 """
@@ -40,6 +45,8 @@ from .mesh import (Mesh, SparseVolume, align_volume, color_mesh, cube_axis,  # n
                    cube_points, eikonal_residual, extract_mesh_sparse,
                    extract_mesh_with_marching_cubes, marching_cubes, normal_mesh, sdf_cube,
                    shade_surface, sparse_extract, world_to_network, xyz2mesh)
+from .raster import (Raster, interpolate_vertex_attributes, load_obj, rasterize_mesh,  # noqa: F401
+                     render_mesh, subdivide_mesh)
 from .options import AttrDict, SDFOptions, vol_render_opt  # noqa: F401
 from . import training  # noqa: F401  (stage-2 DDP trainer, Discriminator, losses)
 from .renderer import (FCGenerator, FiLMSiren, Geometry, LinearLayer,  # noqa: F401

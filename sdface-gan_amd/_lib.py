@@ -60,6 +60,7 @@ EXPORTS = (
     "sdfr_mc_workspace_bytes", "sdfr_mc_count", "sdfr_mc_emit",
     "sdfr_brick_layout_workspace_bytes", "sdfr_brick_layout", "sdfr_brick_points",
     "sdfr_mc_sparse_workspace_bytes", "sdfr_mc_sparse_count", "sdfr_mc_sparse_emit",
+    "sdfr_mesh_raster_workspace_bytes", "sdfr_mesh_raster", "sdfr_mesh_interpolate",
     "sdfr_linear_pack_bytes", "sdfr_linear_pack", "sdfr_linear_f16x3",
     "sdfr_linear_wgrad_ws_bytes", "sdfr_linear_wgrad_f16x3",
     "sdfr_film_linear_f16x3", "sdfr_film_backward_ws_bytes", "sdfr_film_backward",
@@ -189,6 +190,17 @@ class SurfaceArgs(ctypes.Structure):
         ("xyz", _vp), ("normal", _vp), ("rgb", _vp), ("sdf", _vp),
         ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
         ("prepacked", _vp), ("prepacked_grad", _vp),
+    ]
+
+
+class RasterArgs(ctypes.Structure):
+    """sdfr_raster_args (include/sdfr.h)."""
+    _fields_ = [
+        ("B", _u32), ("H", _u32), ("W", _u32), ("V", _u32), ("F", _u32),
+        ("vertices", _vp), ("faces", _vp), ("cam", _vp), ("focal", _vp),
+        ("cx", _f32), ("cy", _f32), ("znear", _f32),
+        ("face_idx", _vp), ("depth", _vp), ("bary", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
     ]
 
 
@@ -371,6 +383,11 @@ def lib():
                                        _vp, ctypes.POINTER(_u32), _vp]
     L.sdfr_mc_sparse_emit.argtypes = [_vp, _vp, _vp, _u32, _u32, _f32, _vp, ctypes.c_size_t,
                                       _vp, _vp, _vp]
+    L.sdfr_mesh_raster_workspace_bytes.argtypes = [_u32] * 5
+    L.sdfr_mesh_raster_workspace_bytes.restype = ctypes.c_size_t
+    L.sdfr_mesh_raster.argtypes = [ctypes.POINTER(RasterArgs), _vp]
+    L.sdfr_mesh_interpolate.argtypes = [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32,
+                                        _vp, _u32, _f32, _vp, _vp]
     L.sdfr_rgb_finish.argtypes = [_vp, _vp, _u32, _vp, _vp, ctypes.POINTER(_f32), _u32, _u32,
                                   _u32, _vp]
     L.sdfr_linear_pack_bytes.argtypes = [_u32, _u32]

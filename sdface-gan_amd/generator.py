@@ -12,8 +12,19 @@ instead of the reference's per-face grouped convolution (same algebra, fp32).
 On the GPU, the bias/leaky-ReLU and upfirdn2d ops are the HIP kernels of
 decoder_ops.py; at inference (no grad) everything between two convolutions is
 one HIP epilogue over channels_last activations (``Decoder._fused_forward``).
-Geometry-aware noise projection (``project_noise``, pytorch3d) is not
-supported and raises.
+
+Geometry-aware noise projection (``Generator.forward(project_noise=True, mesh_path=...)``
+on a model built with ``project_noise``; the reference rasterises with pytorch3d) runs on
+the HIP rasteriser of raster.py: ``NoiseInjection.project_noise`` gives every vertex of the
+identity's mesh one N(0,1) value, rasterises the mesh from the frame's camera at the
+layer's resolution and writes the interpolated values over the layer's fixed noise map
+where the mesh covers a pixel, so the noise follows the surface through a camera sweep.
+The ``Decoder`` forms those maps up front (one rasterisation per resolution) and then runs
+its fused path.  Deliberate differences from the reference: the pose itself and the call's
+focal length (scaled to the layer's resolution) are the camera, where the reference
+rebuilds one from Euler angles at distance 1 and fov 12 degrees (``focal=None`` keeps that
+fov); the nearest face's value, where pytorch3d blends the nearest faces softly; and B >= 1
+views of the one mesh, where the reference asserts B = 1.
 """
 from __future__ import annotations
 
@@ -202,7 +213,48 @@ class ModulatedConv2d(nn.Module):
         return out
 
 
+class ProjectionCache:
+    """What the noise-projecting layers of one ``Decoder`` share: the loaded meshes (one per
+    (path, modification time) or ``Mesh`` object, with their subdivisions) and, during one
+    ``Decoder.forward``, the rasterisation of each distinct (resolution, focal).  A plain
+    object (not a module): every ``NoiseInjection`` of the decoder refers to the same one."""
+
+    def __init__(self):
+        self.meshes = {}
+        self.rasters = None          # a dict only while a Decoder.forward is running
+
+    def clear(self):
+        self.meshes.clear()
+        self.rasters = None
+
+    def mesh(self, mesh_path, times):
+        """``mesh_path`` (an .obj path or a ``Mesh``) subdivided ``times`` times."""
+        from .mesh import Mesh
+        from .raster import load_obj, subdivide_mesh
+        if isinstance(mesh_path, Mesh):
+            key = ("mesh", id(mesh_path))
+            base = mesh_path
+        else:
+            import os
+            path = os.fspath(mesh_path)
+            key = ("path", path, os.stat(path).st_mtime_ns)
+            base = None
+        entry = self.meshes.get(key)
+        if entry is None:
+            # (one identity at a time: a sweep uses one mesh; an older one is dropped)
+            self.meshes.clear()
+            entry = self.meshes[key] = {0: base if base is not None else load_obj(path)}
+        if times not in entry:
+            prev = max(t for t in entry if t < times)
+            entry[times] = subdivide_mesh(entry[prev], times - prev)
+        return entry[times]
+
+
 class NoiseInjection(nn.Module):
+    """``image + weight * noise`` (sdf_model.py:704-792).  Built with ``project=True`` and
+    given a noise map, a camera ``transform`` and a ``mesh_path``, the map is first
+    projected through the mesh (``project_noise``)."""
+
     def __init__(self, project=False):
         super().__init__()
         self.project = project
@@ -210,14 +262,82 @@ class NoiseInjection(nn.Module):
         self.prev_noise = None
         self.mesh_fn = None
         self.vert_noise = None
+        self._vert_noise_dev = None
+        self.shared = ProjectionCache()     # a Decoder replaces it with its own
+        # the image resolution that forward's ``focal`` refers to (None: this layer's own);
+        # a Decoder sets its input resolution, the renderer's out_im_res
+        self.focal_res = None
 
-    def forward(self, image, noise=None, transform=None, mesh_path=None):
+    @staticmethod
+    def subdivisions(res):
+        """The reference's rule (load_mc_mesh, sdf_model.py:728-752): the mesh as loaded up
+        to 128^2, subdivided once at 256^2 and three times above."""
+        return 0 if res <= 128 else (1 if res == 256 else 3)
+
+    def reset_projected_noise(self):
+        self.prev_noise = self.vert_noise = self._vert_noise_dev = self.mesh_fn = None
+
+    def project_noise(self, noise, transform, mesh_path, focal=None, _key=None):
+        """``noise`` [1 or B,1,r,r] with the identity's mesh drawn over it: every vertex of
+        the mesh carries one N(0,1) value (``vert_noise`` [V,1], drawn once on the CPU with
+        ``torch.empty(V, 1).normal_()`` and redrawn only when V changes), the mesh is
+        rasterised from the B cameras ``transform`` [B,3,4] at r x r, and the result is
+        ``where(covered, interpolated vert_noise, prev_noise)`` [B,1,r,r] -- ``prev_noise``
+        being the first map this layer was ever given (it stays the background of every
+        later call, as in the reference, until ``reset_projected_noise``).  So the noise
+        sticks to the surface instead of the screen.  ``mesh_path``: an .obj path or a
+        ``Mesh``; subdivided by ``subdivisions(r)``.  ``focal``: [B], [B,1,1] or a number in
+        pixels of the r x r image; ``None`` is the reference's 12 degree field of view,
+        (r / 2) / tan(6 degrees).
+
+        Differences from the reference (sdf_model.py:754-782), on purpose: the mesh is
+        projected with the pose itself (the reference rebuilds a camera from the pose's
+        Euler angles at distance 1), so the noise lands on the pixels whose rays hit that
+        surface point; the nearest face's value is used, not pytorch3d's soft blend of the
+        nearest faces; B >= 1 views of the one mesh are allowed.  Needs the GPU: one
+        ``sdfr_mesh_raster`` per distinct (r, focal) of a decoder call and one
+        ``sdfr_mesh_interpolate`` per layer."""
+        from .raster import (default_projection_focal, interpolate_vertex_attributes,
+                             rasterize_mesh)
+        if mesh_path is None or transform is None:
+            raise ValueError("project_noise: needs the camera transform and a mesh_path")
+        r = noise.shape[-1]
+        if noise.shape[-2] != r:
+            raise ValueError(f"project_noise: square noise maps only, got {tuple(noise.shape)}")
+        if not noise.is_cuda:
+            raise RuntimeError("project_noise: needs the GPU (HIP kernel)")
+        self.mesh_fn = mesh_path
+        mesh = self.shared.mesh(mesh_path, self.subdivisions(r))
+        V = mesh.vertices.shape[0]
+        if self.vert_noise is None or self.vert_noise.shape[0] != V:
+            self.vert_noise = torch.empty(V, 1).normal_()
+            self._vert_noise_dev = None
+        if self._vert_noise_dev is None or self._vert_noise_dev.device != noise.device:
+            self._vert_noise_dev = self.vert_noise.to(noise.device)
+        if self.prev_noise is None:
+            self.prev_noise = noise
+        if focal is None:
+            focal = default_projection_focal(r)
+        # one rasterisation per resolution of a decoder call (``_key``: forward's, which
+        # names the call's own focal and transform; the decoder holds both while it runs)
+        rasters = self.shared.rasters if _key is not None else None
+        raster = rasters.get(_key) if rasters is not None else None
+        if raster is None:
+            raster = rasterize_mesh(mesh, transform, focal, r)
+            if rasters is not None:
+                rasters[_key] = raster
+        return interpolate_vertex_attributes(mesh, raster, self._vert_noise_dev,
+                                             background=self.prev_noise.to(noise.device))
+
+    def forward(self, image, noise=None, transform=None, mesh_path=None, focal=None):
         batch, _, height, width = image.shape
         if noise is None:
             noise = image.new_empty(batch, 1, height, width).normal_()
-        elif self.project:
-            raise NotImplementedError("geometry-aware noise projection (pytorch3d) is not "
-                                      "part of this framework")
+        elif self.project and transform is not None:
+            key = (height, id(focal), id(transform))
+            if focal is not None and self.focal_res is not None:
+                focal = focal * (height / self.focal_res)
+            noise = self.project_noise(noise, transform, mesh_path, focal, _key=key)
         return image + self.weight * noise
 
 
@@ -231,9 +351,10 @@ class StyledConv(nn.Module):
         self.bias = nn.Parameter(torch.zeros(1, out_channel, 1, 1))
         self.activate = FusedLeakyReLU(out_channel)
 
-    def forward(self, input, style, noise=None, transform=None, mesh_path=None):
+    def forward(self, input, style, noise=None, transform=None, mesh_path=None, focal=None):
         out = self.conv(input, style)
-        out = self.noise(out, noise=noise, transform=transform, mesh_path=mesh_path)
+        out = self.noise(out, noise=noise, transform=transform, mesh_path=mesh_path,
+                         focal=focal)
         return self.activate(out)
 
 
@@ -298,6 +419,13 @@ class Decoder(nn.Module):
             self.to_rgbs.append(ToRGB(out_ch, self.style_dim))
             in_ch = out_ch
         self.n_latent = (self.log_size - self.log_in_size) * 2 + 2
+        # noise projection (project_noise): the layers share one mesh cache and, within a
+        # forward, one rasterisation per resolution; forward's focal is in pixels of the
+        # decoder's input (the renderer's out_im_res)
+        self._proj = ProjectionCache()
+        for sc in [self.conv1] + list(self.convs):
+            sc.noise.shared = self._proj
+            sc.noise.focal_res = dec_in
         self.use_fused = True      # HIP epilogues on the inference path (GPU, no grad)
         # convolutions of the fused path: "f16x3" (split-fp16 MFMA implicit GEMM,
         # csrc/conv_f16x3.hip) or "miopen" (F.conv2d / conv_transpose2d, fp32)
@@ -348,9 +476,54 @@ class Decoder(nn.Module):
                                1)
         return latent, noise
 
+    def reset_projected_noise(self):
+        """Forget what noise projection keeps between calls: every layer's background map
+        (``prev_noise``) and per-vertex noise (``vert_noise``), and the loaded meshes."""
+        for sc in [self.conv1] + list(self.convs):
+            sc.noise.reset_projected_noise()
+        self._proj.clear()
+
+    def _projects(self, transform):
+        return transform is not None and self.conv1.noise.project
+
+    def _projected_noise(self, noise, transform, mesh_path, focal):
+        """The noise maps of a projected call, layer by layer in the module path's order
+        (each layer's ``NoiseInjection.forward`` arithmetic on the map alone): [B,1,r,r]
+        where a map was given, ``None`` (fresh noise) where not."""
+        out = []
+        for sc, n in zip([self.conv1] + list(self.convs), noise):
+            if n is not None:
+                r = n.shape[-1]
+                key = (r, id(focal), id(transform))
+                f = focal if focal is None else focal * (r / sc.noise.focal_res)
+                n = sc.noise.project_noise(n, transform, mesh_path, f, _key=key)
+            out.append(n)
+        return out
+
     def forward(self, features, styles, rgbd_in=None, transform=None, return_latents=False,
                 inject_index=None, truncation=1, truncation_latent=None, input_is_latent=False,
-                noise=None, randomize_noise=True, mesh_path=None, prepared=None):
+                noise=None, randomize_noise=True, mesh_path=None, prepared=None, focal=None):
+        if self._projects(transform):
+            # projected noise: the maps are formed up front (one rasterisation per
+            # resolution, shared by its layers), and the decoder then runs as it does
+            # without a transform -- through the fused path where that applies
+            if mesh_path is None:
+                raise ValueError("Decoder: project_noise needs a mesh_path")
+            self._proj.rasters = {}
+            try:
+                return self._forward(features, styles, rgbd_in, transform, return_latents,
+                                     inject_index, truncation, truncation_latent,
+                                     input_is_latent, noise, randomize_noise, mesh_path,
+                                     prepared, focal)
+            finally:
+                self._proj.rasters = None
+        return self._forward(features, styles, rgbd_in, transform, return_latents,
+                             inject_index, truncation, truncation_latent, input_is_latent,
+                             noise, randomize_noise, mesh_path, prepared, focal)
+
+    def _forward(self, features, styles, rgbd_in, transform, return_latents, inject_index,
+                 truncation, truncation_latent, input_is_latent, noise, randomize_noise,
+                 mesh_path, prepared, focal):
         if prepared is not None:         # prepare_fused() ran earlier (Generator.forward)
             latent, noise, sty = prepared
             if self._fused_ok(features, rgbd_in, transform):
@@ -363,17 +536,22 @@ class Decoder(nn.Module):
             latent, noise = self.styles_and_noise_forward(styles, noise, inject_index,
                                                           truncation, truncation_latent,
                                                           input_is_latent, randomize_noise)
+            if self._projects(transform) and self._fused_ok(features, rgbd_in, None):
+                noise = self._projected_noise(noise, transform, mesh_path, focal)
+                transform = None
             if self._fused_ok(features, rgbd_in, transform):
                 return (self._fused_forward(features, latent, noise),
                         (latent if return_latents else None))
         out = self.conv1(features, latent[:, 0], noise=noise[0], transform=transform,
-                         mesh_path=mesh_path)
+                         mesh_path=mesh_path, focal=focal)
         skip = self.to_rgb1(out, latent[:, 1], skip=rgbd_in)
         i = 1
         for c1, c2, n1, n2, to_rgb in zip(self.convs[::2], self.convs[1::2], noise[1::2],
                                           noise[2::2], self.to_rgbs):
-            out = c1(out, latent[:, i], noise=n1, transform=transform, mesh_path=mesh_path)
-            out = c2(out, latent[:, i + 1], noise=n2, transform=transform, mesh_path=mesh_path)
+            out = c1(out, latent[:, i], noise=n1, transform=transform, mesh_path=mesh_path,
+                     focal=focal)
+            out = c2(out, latent[:, i + 1], noise=n2, transform=transform, mesh_path=mesh_path,
+                     focal=focal)
             skip = to_rgb(out, latent[:, i + 2], skip=skip)
             i += 2
         return skip, (latent if return_latents else None)
@@ -1004,7 +1182,8 @@ class Generator(nn.Module):
                 return_latents=return_latents, inject_index=inject_index, truncation=truncation,
                 truncation_latent=truncation_latent, noise=noise,
                 input_is_latent=input_is_latent, randomize_noise=randomize_noise,
-                mesh_path=mesh_path, prepared=prepared)
+                mesh_path=mesh_path, prepared=prepared,
+                focal=focals if project_noise else None)
         else:
             rgb = None
         if return_latents:
