@@ -888,7 +888,9 @@ int sdfr_conv3x3_f16x3(float *out, const void *x_split, const void *packed,
  * e.g. eval.py's one face) the K-steps of every tile are shared by 2-4 workgroups
  * whose fp32 partial tiles a second kernel sums in a fixed order (deterministic).
  * ws_bytes >= sdfr_conv_ws_bytes(B, H, W, Cout, transposed) enables it (0: no split
- * for this shape; a smaller or NULL workspace runs unsplit). */
+ * for this shape; a smaller or NULL workspace runs unsplit).  The size is the one from
+ * which the launch plan (sdfr_conv_plan below) takes its split, under the current conv_t
+ * mode. */
 int sdfr_conv3x3_f16x3_ws(float *out, const void *x_split, const void *packed,
                           uint32_t B, uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout,
                           int transposed, void *ws, size_t ws_bytes, void *stream);
@@ -966,6 +968,44 @@ typedef struct sdfr_conv_t_act_args {
 } sdfr_conv_t_act_args;
 int sdfr_conv_t_act(const sdfr_conv_t_act_args *a, void *stream);
 int sdfr_conv_t_act_supported(uint32_t B, uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout);
+
+/* The launch plan of one decoder convolution under the current conv_t mode, as the three
+ * entry points above would run it: which kernels, with which grids, after which refusal.
+ * Host arithmetic only (no HIP call, no launch), so tests can pin the dispatch without a
+ * GPU.  Returns info->rc: SDFR_OK, or the code the entry point would refuse the shape
+ * with (sdfr_last_error() then holds the reason); SDFR_EINVAL for null arguments. */
+enum { SDFR_CONV_EPI_RAW = 0,      /* sdfr_conv3x3_f16x3[_ws]                        */
+       SDFR_CONV_EPI_STYLED = 1,   /* sdfr_conv3x3_f16x3_act (transposed = 0)        */
+       SDFR_CONV_EPI_BLUR = 2 };   /* sdfr_conv_t_act        (transposed = 1)        */
+enum { SDFR_CONV_K_X = 0,          /* conv_x_kernel<false>                           */
+       SDFR_CONV_K_X_ACT,          /* conv_x_kernel<true>                            */
+       SDFR_CONV_K_SPLITK,         /* conv_splitk_kernel<false>                      */
+       SDFR_CONV_K_SPLITK_ACT,     /* conv_splitk_kernel<true>                       */
+       SDFR_CONV_K_H,              /* conv_h_kernel<false>                           */
+       SDFR_CONV_K_H_SPLIT,        /* conv_h_kernel<true>                            */
+       SDFR_CONV_K_H_FINISH,       /* conv_h_finish_kernel                           */
+       SDFR_CONV_K_T,              /* conv_t_kernel<false>                           */
+       SDFR_CONV_K_T_FUSE,         /* conv_t_kernel<true>                            */
+       SDFR_CONV_K_T_FINISH,       /* conv_t_finish_kernel                           */
+       SDFR_CONV_K_T_BORDER_ROWS,  /* conv_t_border_kernel<true>                     */
+       SDFR_CONV_K_T_BORDER_COLS };/* conv_t_border_kernel<false>                    */
+#define SDFR_CONV_PLAN_MAX_STEPS 6
+typedef struct sdfr_conv_plan_query {
+    uint32_t B, H, W, Cin, Cout;  /* input H x W                                    */
+    int transposed;
+    int epilogue;                 /* SDFR_CONV_EPI_*                                */
+    int has_ws;                   /* a workspace is offered ...                     */
+    size_t ws_bytes;              /* ... of this size                               */
+} sdfr_conv_plan_query;
+typedef struct sdfr_conv_plan_info {
+    int rc;
+    uint32_t ksplit;              /* split-K factor of conv_x_kernel / conv_h_kernel */
+    uint32_t ksplit_t;            /* channel-group split of conv_t_kernel's tiles   */
+    size_t ws_bytes;              /* workspace from which the path takes its split  */
+    uint32_t nsteps;
+    struct { uint32_t kernel, grid_x, grid_y, block; } steps[SDFR_CONV_PLAN_MAX_STEPS];
+} sdfr_conv_plan_info;
+int sdfr_conv_plan(const sdfr_conv_plan_query *q, sdfr_conv_plan_info *info);
 
 /* ToRGB finish: rgb [B,3,H,W] = sum_k partial[k] + rgb_b[o]
  *   + upfirdn2d(skip, outer(fir,fir), up 2, pad (2,1)) when skip != NULL

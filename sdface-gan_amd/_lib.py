@@ -56,7 +56,7 @@ EXPORTS = (
     "sdfr_conv_pack_bytes", "sdfr_conv_pack_weights", "sdfr_conv3x3_f16x3",
     "sdfr_conv3x3_f16x3_ws", "sdfr_conv_ws_bytes", "sdfr_set_conv_t_mode",
     "sdfr_conv3x3_f16x3_act", "sdfr_conv_act_ws_bytes", "sdfr_rgb_finish",
-    "sdfr_conv_t_act", "sdfr_conv_t_act_supported",
+    "sdfr_conv_t_act", "sdfr_conv_t_act_supported", "sdfr_conv_plan",
     "sdfr_mc_workspace_bytes", "sdfr_mc_count", "sdfr_mc_emit",
     "sdfr_brick_layout_workspace_bytes", "sdfr_brick_layout", "sdfr_brick_points",
     "sdfr_mc_sparse_workspace_bytes", "sdfr_mc_sparse_count", "sdfr_mc_sparse_emit",
@@ -252,6 +252,37 @@ class ConvTActArgs(ctypes.Structure):
     ]
 
 
+# sdfr_conv_plan: SDFR_CONV_EPI_* and the kernels named by SDFR_CONV_K_* (include/sdfr.h)
+CONV_EPI_RAW, CONV_EPI_STYLED, CONV_EPI_BLUR = 0, 1, 2
+CONV_PLAN_KERNELS = (
+    "conv_x_kernel<false>", "conv_x_kernel<true>", "conv_splitk_kernel<false>",
+    "conv_splitk_kernel<true>", "conv_h_kernel<false>", "conv_h_kernel<true>",
+    "conv_h_finish_kernel", "conv_t_kernel<false>", "conv_t_kernel<true>",
+    "conv_t_finish_kernel", "conv_t_border_kernel<true>", "conv_t_border_kernel<false>",
+)
+
+
+class ConvPlanQuery(ctypes.Structure):
+    """sdfr_conv_plan_query (include/sdfr.h)."""
+    _fields_ = [
+        ("B", _u32), ("H", _u32), ("W", _u32), ("Cin", _u32), ("Cout", _u32),
+        ("transposed", _int), ("epilogue", _int), ("has_ws", _int),
+        ("ws_bytes", ctypes.c_size_t),
+    ]
+
+
+class ConvPlanStep(ctypes.Structure):
+    _fields_ = [("kernel", _u32), ("grid_x", _u32), ("grid_y", _u32), ("block", _u32)]
+
+
+class ConvPlanInfo(ctypes.Structure):
+    """sdfr_conv_plan_info (include/sdfr.h)."""
+    _fields_ = [
+        ("rc", _int), ("ksplit", _u32), ("ksplit_t", _u32), ("ws_bytes", ctypes.c_size_t),
+        ("nsteps", _u32), ("steps", ConvPlanStep * 6),
+    ]
+
+
 _lib = None
 
 
@@ -365,6 +396,7 @@ def lib():
     L.sdfr_conv_t_act_supported.restype = _int
     L.sdfr_conv_act_ws_bytes.argtypes = [_u32, _u32, _u32, _u32]
     L.sdfr_conv_act_ws_bytes.restype = ctypes.c_size_t
+    L.sdfr_conv_plan.argtypes = [ctypes.POINTER(ConvPlanQuery), ctypes.POINTER(ConvPlanInfo)]
     _i64 = ctypes.c_int64
     L.sdfr_mc_workspace_bytes.argtypes = [_u32, _u32, _u32]
     L.sdfr_mc_workspace_bytes.restype = ctypes.c_size_t

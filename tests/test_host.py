@@ -119,9 +119,167 @@ def test_conv_split_k_workspace(sdfr):
     assert lib.sdfr_conv_ws_bytes(1, 16, 16, 128, 1) == 4 * 32 * tile
     assert lib.sdfr_conv_ws_bytes(1, 64, 64, 256, 1) == 2 * 152 * tile  # 152 slots: 2-way
     assert lib.sdfr_conv_ws_bytes(1, 128, 128, 128, 1) == 0           # 280 slots: no split
-    # 32 faces: conv_t_kernel (its edge classes unsplit: SDFR_EDGE_SPLIT off)
+    # 32 faces: conv_t_kernel (its edge classes unsplit: splitting them measured slower)
     assert lib.sdfr_conv_ws_bytes(32, 64, 64, 256, 1) == 0
     assert lib.sdfr_conv_ws_bytes(1, 64, 64, 100, 1) == 0             # Cout % 128
+
+
+def _conv_plan(sdfr, B, H, W, Cin, Cout, transposed, epi, ws=None):
+    """sdfr_conv_plan -> (info, [(kernel name, grid x, grid y, block)])."""
+    L = sdfr._lib
+    q = L.ConvPlanQuery(B, H, W, Cin, Cout, int(transposed), epi, int(ws is not None), ws or 0)
+    info = L.ConvPlanInfo()
+    assert L.lib().sdfr_conv_plan(ctypes.byref(q), ctypes.byref(info)) == info.rc
+    steps = [(L.CONV_PLAN_KERNELS[s.kernel], s.grid_x, s.grid_y, s.block)
+             for s in info.steps[:info.nsteps]]
+    return info, steps
+
+
+RAW, STYLED, BLUR = 0, 1, 2
+_TILE = 16 * 512 * 16          # one 128 x 256 fp32 partial tile
+# (B, H, W, Cin, Cout, transposed, epilogue, conv_t mode, workspace offered) -> launches.
+# The decoder's layers (64^2 -> 256^2: styled 256 -> 512, up 512 -> 256, styled 256 -> 256,
+# up 256 -> 128, styled 128 -> 128) and a 512 -> 512 styled layer at 1, 4 and 32 faces.
+_CONV_PLANS = [
+    ((32, 64, 64, 512, 512, 0, STYLED, 1, False), [("conv_h_kernel<false>", 256, 1, 512)]),
+    ((4, 64, 64, 512, 512, 0, STYLED, 1, True), [("conv_h_kernel<false>", 256, 1, 512)]),
+    ((1, 64, 64, 512, 512, 0, STYLED, 1, True),
+     [("conv_h_kernel<true>", 256, 1, 512), ("conv_h_finish_kernel", 64, 4, 128)]),
+    ((1, 64, 64, 512, 512, 0, STYLED, 1, False), [("conv_h_kernel<false>", 64, 1, 512)]),
+    ((1, 64, 64, 256, 512, 0, STYLED, 1, True),
+     [("conv_h_kernel<true>", 256, 1, 512), ("conv_h_finish_kernel", 64, 4, 128)]),
+    ((32, 64, 64, 256, 512, 0, STYLED, 1, True), [("conv_h_kernel<false>", 256, 1, 512)]),
+    ((1, 128, 128, 256, 256, 0, STYLED, 1, True),
+     [("conv_h_kernel<true>", 256, 1, 512), ("conv_h_finish_kernel", 128, 4, 128)]),
+    ((4, 128, 128, 256, 256, 0, STYLED, 1, True), [("conv_h_kernel<false>", 256, 1, 512)]),
+    ((1, 256, 256, 128, 128, 0, STYLED, 1, True), [("conv_h_kernel<false>", 256, 1, 512)]),
+    ((32, 256, 256, 128, 128, 0, STYLED, 1, True), [("conv_h_kernel<false>", 256, 1, 512)]),
+    # the upsampling convs, raw output
+    ((32, 64, 64, 512, 256, 1, RAW, 1, True),
+     [("conv_t_kernel<false>", 256, 1, 512), ("conv_x_kernel<false>", 72, 1, 512)]),
+    ((4, 64, 64, 512, 256, 1, RAW, 1, True),
+     [("conv_t_kernel<false>", 256, 1, 512), ("conv_x_kernel<false>", 32, 1, 512)]),
+    ((1, 64, 64, 512, 256, 1, RAW, 1, True),
+     [("conv_x_kernel<false>", 152, 2, 512), ("conv_splitk_kernel<false>", 152, 1, 512)]),
+    ((1, 64, 64, 512, 256, 1, RAW, 1, False), [("conv_x_kernel<false>", 152, 1, 512)]),
+    ((32, 64, 64, 512, 256, 1, RAW, 0, True), [("conv_x_kernel<false>", 4168, 1, 512)]),
+    ((1, 64, 64, 512, 256, 1, RAW, 2, True),
+     [("conv_t_kernel<false>", 64, 1, 512), ("conv_x_kernel<false>", 32, 1, 512)]),
+    ((1, 64, 64, 512, 256, 1, RAW, 3, True),
+     [("conv_t_kernel<false>", 256, 1, 512), ("conv_t_finish_kernel", 4096, 1, 256),
+      ("conv_x_kernel<false>", 32, 1, 512)]),
+    ((1, 64, 64, 512, 256, 1, RAW, 3, False),
+     [("conv_t_kernel<false>", 64, 1, 512), ("conv_x_kernel<false>", 32, 1, 512)]),
+    ((32, 128, 128, 256, 128, 1, RAW, 1, True),
+     [("conv_t_kernel<false>", 256, 1, 512), ("conv_x_kernel<false>", 72, 1, 512)]),
+    ((4, 128, 128, 256, 128, 1, RAW, 1, True),
+     [("conv_t_kernel<false>", 256, 1, 512), ("conv_x_kernel<false>", 32, 1, 512)]),
+    ((1, 128, 128, 256, 128, 1, RAW, 1, True), [("conv_x_kernel<false>", 280, 1, 512)]),
+    # ... and with the blur and the styled epilogue fused (sdfr_conv_t_act)
+    ((32, 64, 64, 512, 256, 1, BLUR, 1, False),
+     [("conv_t_kernel<true>", 256, 1, 512), ("conv_x_kernel<false>", 72, 1, 512),
+      ("conv_t_border_kernel<true>", 1280, 1, 256), ("conv_t_border_kernel<false>", 1280, 1, 256)]),
+    ((4, 64, 64, 512, 256, 1, BLUR, 1, False),
+     [("conv_t_kernel<true>", 256, 1, 512), ("conv_x_kernel<false>", 32, 1, 512),
+      ("conv_t_border_kernel<true>", 160, 1, 256), ("conv_t_border_kernel<false>", 160, 1, 256)]),
+    ((32, 128, 128, 256, 128, 1, BLUR, 1, False),
+     [("conv_t_kernel<true>", 256, 1, 512), ("conv_x_kernel<false>", 72, 1, 512),
+      ("conv_t_border_kernel<true>", 2304, 1, 256), ("conv_t_border_kernel<false>", 2304, 1, 256)]),
+    ((1, 64, 64, 512, 256, 1, BLUR, 2, False),
+     [("conv_t_kernel<true>", 64, 1, 512), ("conv_x_kernel<false>", 32, 1, 512),
+      ("conv_t_border_kernel<true>", 40, 1, 256), ("conv_t_border_kernel<false>", 40, 1, 256)]),
+]
+
+
+@pytest.mark.parametrize("shape,want", _CONV_PLANS)
+def test_conv_plan_dispatch(sdfr, shape, want):
+    """The launches of the decoder's convolutions (sdfr_conv_plan: host arithmetic, no
+    launch): kernel, grid and workgroup size per step, read off the dispatch code; and the
+    size queries agree with the plan -- with exactly the reported workspace the plan takes
+    its split, with one byte fewer it does not."""
+    B, H, W, Cin, Cout, tr, epi, mode, offer = shape
+    lib = sdfr._lib.lib()
+    prev = lib.sdfr_set_conv_t_mode(mode)
+    try:
+        free, _ = _conv_plan(sdfr, B, H, W, Cin, Cout, tr, epi)
+        assert free.rc == 0 and free.ksplit == 1 and free.ksplit_t == 1
+        need = free.ws_bytes
+        if epi == STYLED:
+            assert lib.sdfr_conv_act_ws_bytes(B, H, W, Cout) == need
+        elif epi == RAW:
+            assert lib.sdfr_conv_ws_bytes(B, H, W, Cout, tr) == need
+        else:
+            assert need == 0 and lib.sdfr_conv_t_act_supported(B, H, W, Cin, Cout) == 1
+        info, steps = _conv_plan(sdfr, B, H, W, Cin, Cout, tr, epi, need if offer else None)
+        assert info.rc == 0 and info.ws_bytes == need
+        assert steps == want
+        split = info.ksplit * info.ksplit_t
+        assert (split > 1) == (offer and need > 0)
+        if need:
+            short, _ = _conv_plan(sdfr, B, H, W, Cin, Cout, tr, epi, need - 1)
+            assert short.rc == 0 and short.ksplit == 1 and short.ksplit_t == 1
+    finally:
+        lib.sdfr_set_conv_t_mode(prev)
+
+
+def test_conv_plan_split_factors_and_refusals(sdfr):
+    L = sdfr._lib
+    lib = L.lib()
+    prev = lib.sdfr_set_conv_t_mode(1)
+    try:
+        info, _ = _conv_plan(sdfr, 1, 64, 64, 512, 512, 0, STYLED, 4 * 64 * _TILE)
+        assert (info.ksplit, info.ksplit_t, info.ws_bytes) == (4, 1, 4 * 64 * _TILE)
+        info, _ = _conv_plan(sdfr, 1, 64, 64, 512, 256, 1, RAW, 2 * 152 * _TILE)
+        assert (info.ksplit, info.ksplit_t, info.ws_bytes) == (2, 1, 2 * 152 * _TILE)
+        # 96 channels = 3 groups: conv_h_kernel's split takes whole groups, 4 -> 3
+        info, steps = _conv_plan(sdfr, 1, 64, 64, 96, 512, 0, STYLED, 4 * 64 * _TILE)
+        assert info.ksplit == 3 and steps[0] == ("conv_h_kernel<true>", 192, 1, 512)
+        # H or W not a multiple of 16: the strip kernel carries the styled epilogue
+        info, steps = _conv_plan(sdfr, 1, 8, 32, 64, 128, 0, STYLED, 4 * 8 * _TILE)
+        assert steps == [("conv_x_kernel<true>", 8, 4, 512), ("conv_splitk_kernel<true>", 8, 1, 512)]
+        # below conv_t_kernel's range the fused upsampling conv is refused (mode 1), ...
+        info, steps = _conv_plan(sdfr, 1, 64, 64, 512, 256, 1, BLUR)
+        assert info.rc == L.SDFR_EUNSUPPORTED and steps == []
+        assert b"below conv_t_kernel's range" in lib.sdfr_last_error()
+        assert lib.sdfr_conv_t_act_supported(1, 64, 64, 512, 256) == 0
+        lib.sdfr_set_conv_t_mode(2)            # ... in mode 2 it is taken at any tile count
+        info, _ = _conv_plan(sdfr, 1, 64, 64, 512, 256, 1, BLUR)
+        assert info.rc == 0 and lib.sdfr_conv_t_act_supported(1, 64, 64, 512, 256) == 1
+        lib.sdfr_set_conv_t_mode(3)            # mode 3: 4 x 129^2 x 256 fp32 partial outputs
+        info, _ = _conv_plan(sdfr, 1, 64, 64, 512, 256, 1, RAW, 4 * 129 * 129 * 256 * 4)
+        assert (info.ksplit, info.ksplit_t, info.ws_bytes) == (1, 4, 4 * 129 * 129 * 256 * 4)
+        assert lib.sdfr_conv_ws_bytes(1, 64, 64, 256, 1) == info.ws_bytes
+        # bad channel counts and the 2^31-byte offset limit
+        for bad in ((1, 64, 64, 500, 256, 0, RAW), (1, 64, 64, 512, 100, 1, RAW)):
+            info, steps = _conv_plan(sdfr, *bad)
+            assert info.rc == L.SDFR_EINVAL and steps == [] and b"bad shape" in lib.sdfr_last_error()
+        info, _ = _conv_plan(sdfr, 64, 256, 256, 128, 128, 0, STYLED)
+        assert info.rc == L.SDFR_EINVAL and b"32-bit offsets" in lib.sdfr_last_error()
+        info, _ = _conv_plan(sdfr, 1, 64, 64, 512, 256, 1, STYLED)
+        assert info.rc == L.SDFR_EINVAL
+    finally:
+        lib.sdfr_set_conv_t_mode(prev)
+
+
+def test_conv_t_act_rejects_misaligned_noise(sdfr):
+    """conv_t_kernel<true> reads the noise with 16-B loads: a misaligned pointer is refused
+    with the other vector-loaded tensors, before any launch (integers stand in for
+    pointers: nothing is dereferenced)."""
+    L = sdfr._lib
+    lib = L.lib()
+    a = L.ConvTActArgs()
+    a.x_split, a.packed = 0x10000, 0x20000
+    a.B, a.H, a.W, a.Cin, a.Cout = 1, 16, 16, 32, 128
+    a.demod, a.bias, a.noise_weight, a.s_next = 0x30000, 0x40000, 0x50000, 0x60000
+    a.y_split, a.raw = 0x70000, 0x80000
+    a.noise = 0x90000 + 4
+    prev = lib.sdfr_set_conv_t_mode(2)
+    try:
+        assert lib.sdfr_conv_t_act_supported(1, 16, 16, 32, 128) == 1
+        assert lib.sdfr_conv_t_act(ctypes.byref(a), None) == L.SDFR_EINVAL
+        assert b"16-B aligned" in lib.sdfr_last_error()
+    finally:
+        lib.sdfr_set_conv_t_mode(prev)
 
 
 def test_fused_decoder_batch_chunk(sdfr):
