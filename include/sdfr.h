@@ -641,19 +641,6 @@ int sdfr_render_ngp_surface(const sdfr_ngp_weights *w, const sdfr_surface_args *
 int sdfr_render_siren_surface(const sdfr_siren_weights *w, const sdfr_surface_args *a,
                               void *stream);
 
-#ifdef SDFR_ABLATION
-/* Profiling hooks, exported only by `make ABLATION=1` builds (lib_abl/libsdfr.so,
- * process-global state; never in the product library):
- * sdfr_debug_set_field_variant selects an ablated field kernel for later calls
- * (0 = the product kernel; 1 no barrier, 2 no LDS A-operand reads, 4 no weight
- * staging, 8 no activations, 16 no compositing, 15/31 MFMA only -- wrong outputs,
- * to attribute kernel time); sdfr_debug_set_encode_mode the
- * hash-grid gather variant (default 289, or SDFR_ENC_MODE at load; 1, 2, 9, 33,
- * 257, 289, 290 -- all bit-identical, scripts/encode_time.py). */
-int sdfr_debug_set_field_variant(int variant);
-int sdfr_debug_set_encode_mode(int mode);
-#endif
-
 /* Accuracy probe for the two device sin implementations the field kernel can
  * use (software Cody-Waite + polynomial, hardware v_sin_f32 after reduction):
  * out_cw[i] = sin_cw(x[i]), out_hw[i] = sin_hw(x[i]), n elements. */

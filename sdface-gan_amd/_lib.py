@@ -27,9 +27,8 @@ ABI_VERSION = 15
 FIELD_F16X3 = 0
 FIELD_FP32 = 1
 
-# every symbol include/sdfr.h declares outside its SDFR_ABLATION block (tests check the
-# product .so exports all of them and nothing else with the sdfr_ prefix)
-ABLATION_EXPORTS = ("sdfr_debug_set_field_variant", "sdfr_debug_set_encode_mode")
+# every symbol include/sdfr.h declares (tests check the .so exports all of them and
+# nothing else with the sdfr_ prefix)
 EXPORTS = (
     "sdfr_abi_version", "sdfr_last_error",
     "sdfr_grid_encode_forward", "sdfr_grid_encode_backward",
@@ -332,9 +331,6 @@ def lib():
         size.argtypes = [_u32, _u32, _u32, _u32]
         getattr(L, f"sdfr_render_{net}_surface").argtypes = [
             ctypes.POINTER(weights), ctypes.POINTER(SurfaceArgs), _vp]
-    for name in ABLATION_EXPORTS:           # profiling builds only (make ABLATION=1)
-        if hasattr(L, name):
-            getattr(L, name).argtypes = [_int]
     L.sdfr_render_siren_workspace_bytes.restype = ctypes.c_size_t
     L.sdfr_render_siren_workspace_bytes.argtypes = [_u32]
     L.sdfr_render_pack_bytes.argtypes = [_int]

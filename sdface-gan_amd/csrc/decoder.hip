@@ -382,25 +382,13 @@ __global__ __launch_bounds__(256) void epi_plain_kernel(EpiArgs a, uint32_t tpp_
 // Blur epilogue: thread = (face, row segment, column, channel quad); a sliding
 // window of 4 horizontally filtered input rows gives the 4x4 separable blur
 // with one new 16-B load per tap column per output row.
-#ifndef BLUR_ROWS
-#define BLUR_ROWS 16
-#endif
-#ifndef BLUR_GROUP
-#define BLUR_GROUP 4
-#endif
-constexpr uint32_t kBlurRows = BLUR_ROWS;
-constexpr int kBlurGroup = BLUR_GROUP;   // input rows loaded together (kBlurRows % it == 0)
-#ifndef BLUR_COLS
-#define BLUR_COLS 4
-#endif
-constexpr int kBlurCols = BLUR_COLS;     // adjacent output columns per thread
+constexpr uint32_t kBlurRows = 16;
+constexpr int kBlurGroup = 4;   // input rows loaded together (kBlurRows % it == 0)
+constexpr int kBlurCols = 4;    // adjacent output columns per thread
 // XCD-aware block order: the dispatcher deals blocks round-robin over the 8 XCDs, so
 // logically adjacent blocks (which share 3 input columns) would each fill the shared
 // lines into a different L2; remapped, blocks p and p + 8 (same XCD, dispatched
 // together) take adjacent column groups.  The grid is padded to a multiple of 8.
-#ifndef BLUR_XCD
-#define BLUR_XCD 1
-#endif
 
 // rps: output rows per segment (a multiple of kBlurGroup, at most kBlurRows): small
 // batches use shorter segments so the grid still covers the chip
@@ -408,8 +396,7 @@ __global__ __launch_bounds__(256) void epi_blur_kernel(EpiArgs a, uint32_t nseg,
     constexpr int NC = kBlurCols;                     // output columns per thread
     const uint32_t Q = a.C >> 2;
     const uint32_t WG = (a.W + NC - 1) / NC;           // column groups
-    uint32_t bid = blockIdx.x;
-    if (BLUR_XCD) bid = (bid & 7u) * (gridDim.x >> 3) + (bid >> 3);
+    const uint32_t bid = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     // (32-bit index arithmetic: the host keeps the thread count below 2^31)
     const uint32_t t = bid * blockDim.x + threadIdx.x;
     const uint32_t total = a.B * nseg * WG * Q;
@@ -983,7 +970,7 @@ int sdfr_styled_epilogue(const sdfr_styled_epilogue_args *p, void *stream) {
         }
         if (total >= (1ull << 31)) return fail(SDFR_EINVAL, "styled_epilogue(blur): too large");
         const uint32_t nb = (uint32_t)((total + 255) / 256);
-        epi_blur_kernel<<<BLUR_XCD ? (nb + 7) & ~7u : nb, 256, 0, st>>>(a, nseg, rps);
+        epi_blur_kernel<<<(nb + 7) & ~7u, 256, 0, st>>>(a, nseg, rps);
         return check_launch("styled_epilogue(blur)");
     }
     const uint32_t Q = s.C / 4;

@@ -24,7 +24,7 @@
 // gamma is divided by su (gamma' x_scaled == gamma x, bit for bit), the layer bias
 // folds into the FiLM beta, and the feature scale is taken out in layer 0's FiLM.
 //
-// Work unit (field_r_kernel, field_f16x3_kernels.h): a workgroup of 4 waves, one per SIMD (512
+// Work unit (field_r_kernel, field_r.h): a workgroup of 4 waves, one per SIMD (512
 // VGPRs), over 4 tiles of 16 rays; each wave computes ALL 256 output rows of every
 // layer for 32 samples (16 rays x 2 consecutive samples), so a layer's accumulators,
 // activated and split in place, are the next layer's B fragments (no LDS hand-off).
@@ -35,15 +35,19 @@
 // 16 KB half-slices per k-step of 32 K), which is 6 % faster on its nine FiLM layers
 // -- the one-wave kernel's 32x32 MFMAs hold a lower clock there (1.64 GHz, counters).
 //
-// The kernel templates are in field_f16x3_kernels.h.  This unit holds the render's
-// instantiations of them with their launches (launch_xprep, launch_xfield), the
-// non-template kernels (xscale_kernel, compose_kernel, field_merge_kernel) and the
-// sample-segment rule (field_nseg).  The entry points that call them are in render_api.hip.
+// The kernel templates are in field_pack.h, field_p.h and field_r.h (what they share in
+// field_common.h).  This unit holds the render's instantiations of them with their
+// launches (launch_xprep, launch_xfield), the non-template kernels (xscale_kernel,
+// compose_kernel, field_merge_kernel) and the sample-segment rule (field_nseg).  The entry
+// points that call them are in render_api.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "field_f16x3_kernels.h"
+#include "field_common.h"
+#include "field_pack.h"
+#include "field_p.h"
+#include "field_r.h"
 #include "render_launch.h"
 
 namespace sdfr {

@@ -17,7 +17,7 @@
 // co-compiled instantiations of one kernel template share register-allocation context, so
 // a second one there would move the ngp query kernel's code.  Built with the field units'
 // flags.
-#include "field_f16x3_kernels.h"
+#include "field_r.h"
 
 namespace sdfr {
 

@@ -29,7 +29,7 @@
 //
 // Field kernel: the k-step loop, the LDS-DMA weight ring and the in-register hand-off of
 // activated accumulators as the next layer's B fragments are field_r_kernel's (rstep,
-// field_f16x3_kernels.h), run on the first 2 + 32 slices of the same packed weights with the same
+// field_r.h), run on the first 2 + 32 slices of the same packed weights with the same
 // FiLM vectors.  A wave's 32 MFMA columns are 8 points x {value, d/du_0, d/du_1, d/du_2},
 // a point's four columns in adjacent lanes (column c = 4 point + kind).  Per accumulator
 // register, with z the GEMM output of the lane's own column and u = fma(gamma'', z_value,
@@ -45,9 +45,10 @@
 // (field_r_kernel's es).  An all-zero column (a point outside the box) keeps exponent 0.
 // The last layer's tangents feed fp32 fmas only and are not rescaled.
 //
-// This unit takes field_f16x3_kernels.h for its templates and helpers and instantiates
-// nothing of the render's; it is built with the field kernels' flags.
-#include "field_f16x3_kernels.h"
+// This unit takes field_pack.h and field_r.h for their templates and helpers and
+// instantiates nothing of the render's; it is built with the field kernels' flags.
+#include "field_pack.h"
+#include "field_r.h"
 
 namespace sdfr {
 

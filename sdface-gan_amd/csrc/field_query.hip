@@ -8,7 +8,7 @@
 //                                read from memory, no compositing, and a per-sample
 //                                store of the SDF and the colour
 //
-// The field kernel is the template of field_f16x3_kernels.h, instantiated HERE and nowhere
+// The field kernel is the template of field_r.h, instantiated HERE and nowhere
 // else: co-compiled instantiations of one kernel template share register-allocation
 // context, so a query instantiation beside the render's would move the render kernels'
 // code.  This unit is built with field_f16x3.hip's flags.
@@ -17,7 +17,8 @@
 // wave-pair kernel with the point and the group's direction read from memory.  It has no
 // gather and no staging kernel.  field_r_kernel<NgpQueryNet> comes out of the compiler
 // unchanged beside it (profiles/siren_query_isa.txt).
-#include "field_f16x3_kernels.h"
+#include "field_p.h"
+#include "field_r.h"
 
 namespace sdfr {
 

@@ -368,10 +368,7 @@ __global__ void __launch_bounds__(kLinThreads) lin_fwd_kernel(const LinArgs a) {
 // Block (f, j) covers rows [f R + j rpb, ...) of face f; thread = column (N = 256).
 // ----------------------------------------------------------------------------
 // rows per thread whose loads are issued together (film_bwd / film_bwd2_kernel)
-#ifndef SDFR_FILM_ROWS
-#define SDFR_FILM_ROWS 4
-#endif
-constexpr int kFilmRows = SDFR_FILM_ROWS;
+constexpr int kFilmRows = 4;
 
 __global__ void __launch_bounds__(256) film_bwd_kernel(const float *__restrict__ ds,
                                                        const float *__restrict__ y,

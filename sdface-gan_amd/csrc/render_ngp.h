@@ -1,6 +1,6 @@
 // render_ngp.h -- device helpers and kernel-argument structs shared by the fused
 // renderer's kernel units (render_ngp.hip: prep, hash-grid encode, fp32-MFMA field kernel;
-// field_f16x3_kernels.h: the split-fp16 MFMA field kernels; geometry.hip).  The host-side
+// field_r.h, field_p.h: the split-fp16 MFMA field kernels; geometry.hip).  The host-side
 // launch functions those units export are declared in render_launch.h.
 #pragma once
 

@@ -1,8 +1,8 @@
 // render_ngp.hip -- fused SDF + hash-grid volume renderer for MI355X (gfx950).
 //
 // The kernels of the ngp render's own stages and their launches (the entry point,
-// sdfr_render_ngp_forward, is in render_api.hip), and the camera / sin-probe / ablation
-// entry points, which launch their kernels directly.
+// sdfr_render_ngp_forward, is in render_api.hip), and the camera / sin-probe entry
+// points, which launch their kernels directly.
 //
 // Replaces VolumeFeatureRenderer.forward for rendering.type == "ngp"
 // (sdf_model.py:411-423 -> render :363 -> render_rays :310 ->
@@ -38,7 +38,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <string>
 
 #include "render_launch.h"
@@ -126,23 +125,21 @@ struct EncodeArgs {
     int pair_ok;                   // table 16-B aligned (paired corner loads)
 };
 
-// Encode launch options (sdfr_debug_set_encode_mode / SDFR_ENC_MODE, ablations
-// only; all bit-identical; times per 32 faces from scripts/encode_time.py):
-//  +8 off   PAIR: the x-neighbour corners (g0, g0+1) from one aligned 16-B load
-//           whenever their rows are {i, i^1} (hash prime 1 on x: always for
-//           even g0; dense rows: for even i), an 8-B load of the second row
-//           only for the other lanes.                      mode 9 0.94 -> 1 0.84 ms
-//  +256     A8: the same with dword-aligned 16-B loads, so ANY consecutive rows
-//           i, i+-1 come from one load (every dense row, 2/3 of the hashed
-//           g0 parities).                                       -> 257 0.80 ms
-//  low bits LPT levels per thread {y, y+16/LPT} (2: mode 2 0.83 ms; 4 was
-//           slower, 1.17 ms, with four levels' tables live in each L2).
-//  +32      SPT = 2 samples per thread, 256 apart: twice the corner loads in
-//           flight per wave.                                    -> 289 0.77 ms
-//           Since the per-sample coordinate comes precomputed (sample_geom_kernel)
-//           one sample per thread is faster again: 257 0.787 vs 289 0.803 ms (and
-//           258, two levels per thread, 0.824), interleaved on one box, geom
-//           kernel included.
+// The gather: one (sample, level) per thread, the two x-neighbour corners (g0, g0 + 1) of
+// each of the four (y, z) corner pairs from ONE dword-aligned 16-B load whenever their rows
+// are consecutive (i, i +- 1: every dense row, 2/3 of the hashed g0 parities), an 8-B load
+// of the second row only for the other lanes (load_xpair, sdfr_common.h).
+// Why this form (all candidates bit-identical; ms per 32 faces, measured with kernel
+// variants that were compile-time options of this unit up to commit a4b3009; an experiment
+// is now a patch on a scratch copy):
+//   six separate 8-B corner loads                                          0.94
+//   16-B ALIGNED pair loads (rows {i, i^1} only: even g0 / even dense i)   0.84
+//   dword-aligned pair loads (this kernel)                                 0.80
+//   two levels per thread {y, y + 8}: 0.83; four: 1.17 (four levels' tables live in each L2)
+//   two samples per thread, 256 apart: 0.77 while the thread still computed its sample's
+//   coordinate; since that comes precomputed (sample_geom_kernel) one sample per thread is
+//   faster again, 0.787 vs 0.803 (two levels per thread 0.824), interleaved on one box,
+//   geom kernel included.
 // The gather is bound by L1 tag lookups (one 128-B line per lane per load
 // instruction, ~54 cycles per wave-load measured): the wins above all cut
 // load instructions per sample-level (6 -> ~4.9).  Measured and dropped:
@@ -150,62 +147,10 @@ struct EncodeArgs {
 // sc1 (L2-dropping) output stores (+-1%), adjacent level pairs {2y, 2y+1}
 // (1.09 ms), whole image rows per wave (0.86 ms), 4 samples per thread (0.78 ms),
 // nontemporal table loads (2.1 ms: the table no longer stays in L2).
-constexpr uint32_t kEncDefault = 256 | 1;
 
-// level_interp<3,2> with paired x-corner loads: the same corner weights
-// (x factor first, then y, z) and the same fma order over corners 0..7, so the
-// result is bit-identical to level_interp.
-__device__ __forceinline__ void level_interp_pair(const float *__restrict__ grid,
-                                                  const LevelParam &q,
-                                                  const LevelCoord<3, 2> &lc, float (&out)[2]) {
-    float v[8][2];
-    float wts[8];
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; idx += 2) {
-        uint32_t pl[3];
-        float w0 = __fsub_rn(1.0f, lc.pos[0]), w1 = lc.pos[0];
-#pragma unroll
-        for (uint32_t d = 1; d < 3; ++d) {
-            const bool hi = idx & (1u << d);
-            pl[d] = hi ? lc.pg[d] + 1 : lc.pg[d];
-            const float f = hi ? lc.pos[d] : __fsub_rn(1.0f, lc.pos[d]);
-            w0 = __fmul_rn(w0, f);
-            w1 = __fmul_rn(w1, f);
-        }
-        wts[idx] = w0;
-        wts[idx + 1] = w1;
-        pl[0] = lc.pg[0];
-        const uint32_t i0 = grid_index<3>(q, 0, pl);
-        pl[0] = lc.pg[0] + 1;
-        const uint32_t i1 = grid_index<3>(q, 0, pl);
-        const float4 t = *reinterpret_cast<const float4 *>(grid + (size_t)(i0 & ~1u) * 2);
-        const bool odd = i0 & 1u;
-        v[idx][0] = odd ? t.z : t.x;
-        v[idx][1] = odd ? t.w : t.y;
-        if (i1 == (i0 ^ 1u)) {
-            v[idx + 1][0] = odd ? t.x : t.z;
-            v[idx + 1][1] = odd ? t.y : t.w;
-        } else {
-            const float2 u = *reinterpret_cast<const float2 *>(grid + (size_t)i1 * 2);
-            v[idx + 1][0] = u.x;
-            v[idx + 1][1] = u.y;
-        }
-    }
-    out[0] = out[1] = 0.0f;
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; ++idx)
-#pragma unroll
-        for (uint32_t c = 0; c < 2; ++c) out[c] = __fmaf_rn(wts[idx], v[idx][c], out[c]);
-}
-
-// One thread: SPT samples (256 apart) x LPT levels ({y, y+16/LPT, ...}, or
-// {LPT y, LPT y + 1, ...} with ADJ).  Branch-free: padding / out-of-box samples
-// gather at u = 0.5 and store 0, so every corner load of the thread can be in
-// flight at once.
-// level_interp_pair with dword-aligned (not 16-B aligned) pair loads
-// (load_xpair, sdfr_common.h): the two x-corners come from ONE 16-B load
-// whenever their rows are consecutive.  Same weights and fma order as
-// level_interp: bit-identical.
+// level_interp<3,2> with dword-aligned (not 16-B aligned) pair loads (load_xpair,
+// sdfr_common.h): the same corner weights (x factor first, then y, z) and the same fma
+// order over corners 0..7, so the result is bit-identical to level_interp.
 __device__ __forceinline__ void level_interp_adj(const float *__restrict__ grid,
                                                  const LevelParam &q,
                                                  const LevelCoord<3, 2> &lc, float (&out)[2]) {
@@ -238,10 +183,12 @@ __device__ __forceinline__ void level_interp_adj(const float *__restrict__ grid,
         for (uint32_t c = 0; c < 2; ++c) out[c] = __fmaf_rn(wts[idx], v[idx][c], out[c]);
 }
 
-// One thread: SPT samples (256 apart) x LPT levels {y, y + 16/LPT, ...}.
-// Branch-free: padding / out-of-box samples gather at u = 0.5 and store 0, so
-// every corner load of the thread can be in flight at once.
-template <bool PAIR, bool A8, uint32_t LPT, uint32_t SPT>
+// One thread: SPT samples (256 apart) x LPT levels {y, y + 16/LPT, ...}; the product is
+// <1, 1>, one sample of level blockIdx.y (see the record above).  The two parameters stay
+// because the compiler's output for <1, 1> moves when its single-trip loops are written
+// out.  Branch-free: padding / out-of-box samples gather at u = 0.5 and store 0, so every
+// corner load of the thread can be in flight at once.
+template <uint32_t LPT, uint32_t SPT>
 __global__ void __launch_bounds__(256) ngp_encode_kernel(const EncodeArgs a) {
     float2 *out = reinterpret_cast<float2 *>(a.enc);
     uint32_t sid[SPT];
@@ -266,19 +213,17 @@ __global__ void __launch_bounds__(256) ngp_encode_kernel(const EncodeArgs a) {
         LevelParam q = a.lt.p[level];
         finish_level(q, a.offsets, level, 3, 0, 0);
         const float *grid = a.emb + (size_t)q.offset * 2;
-        // pairs are 16-B aligned when the level base (offset) is even and the
-        // table itself is 16-B aligned (host check, a.pair_ok); an even level
-        // size keeps every aligned pair inside the level
-        const bool pair = PAIR && a.pair_ok && !((q.offset | q.hsize) & 1u);
+        // pair loads need the table itself 16-B aligned (host check, a.pair_ok) and an
+        // even level base (offset); an even level size keeps every pair inside the
+        // level.  Otherwise the plain corner loads of level_interp.
+        const bool pair = a.pair_ok && !((q.offset | q.hsize) & 1u);
 #pragma unroll
         for (uint32_t k = 0; k < SPT; ++k) {
             LevelCoord<3, 2> lc;
             level_coord<3, 2>(u[k], q, 0, 0, lc);
             float res[2];
-            if (pair && A8)
+            if (pair)
                 level_interp_adj(grid, q, lc, res);
-            else if (pair)
-                level_interp_pair(grid, q, lc, res);
             else
                 level_interp<3, 2>(grid, q, 0, lc, res);
             if (live[k])
@@ -473,13 +418,7 @@ struct NoSide {
 // `side` is register work (the previous layer's activation of one tile, the
 // compositing math...) placed in the same basic block as the MFMAs, so the
 // scheduler issues it in the MFMA shadow instead of after the layer.
-// Ablation variants (profiling builds only, selected by
-// sdfr_debug_set_field_variant; V = 0 is the product): bit 0 drops the
-// barrier, bit 1 the LDS A-operand reads, bit 2 the ring staging, bit 3 the
-// activations.  Any V != 0 computes wrong results by construction.
-enum : int { ABL_BARRIER = 1, ABL_LDSREAD = 2, ABL_STAGE = 4, ABL_ACT = 8 };
-
-template <int V, class Side>
+template <class Side>
 __device__ __forceinline__ void ring_step(Ring &R, f4 (&acc)[16], const f4 bq, Side &&side) {
     const uint32_t cur = R.it % 3u, nxt = (R.it + 1u) % 3u;
     // all 16 A-operand quads of this slice are read up front (one LDS latency
@@ -488,7 +427,7 @@ __device__ __forceinline__ void ring_step(Ring &R, f4 (&acc)[16], const f4 bq, S
     const f4 *A = R.lds + cur * kSliceF4 + (R.tid & 63u);
     f4 a[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) a[i] = (V & ABL_LDSREAD) ? bq * (float)(i + 1) : A[i * 64];
+    for (int i = 0; i < 16; ++i) a[i] = A[i * 64];
 #pragma unroll
     for (int grp = 0; grp < 4; ++grp) {
 #pragma unroll
@@ -505,20 +444,17 @@ __device__ __forceinline__ void ring_step(Ring &R, f4 (&acc)[16], const f4 bq, S
             acc[4 * grp + i] = mfma4(a[4 * grp + i].w, bq.w, acc[4 * grp + i]);
     }
     side();
-    if constexpr (!(V & ABL_STAGE)) {
-        // slice it+1 (loaded at the end of the previous slice, so it had this
-        // slice's whole MFMA body to land) -> LDS slot; then slice it+2 -> regs.
-        // Writing at the END keeps the LDS writes out of the way of this
-        // slice's A-operand reads.
-        __builtin_amdgcn_sched_barrier(0);
+    // slice it+1 (loaded at the end of the previous slice, so it had this
+    // slice's whole MFMA body to land) -> LDS slot; then slice it+2 -> regs.
+    // Writing at the END keeps the LDS writes out of the way of this
+    // slice's A-operand reads.
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < kStageF4; ++i) R.lds[nxt * kSliceF4 + R.tid + i * kThreads] = R.st[i];
-        const uint32_t pf = (R.it + 2u) % kSlices;
+    for (int i = 0; i < kStageF4; ++i) R.lds[nxt * kSliceF4 + R.tid + i * kThreads] = R.st[i];
+    const uint32_t pf = (R.it + 2u) % kSlices;
 #pragma unroll
-        for (int i = 0; i < kStageF4; ++i)
-            R.st[i] = R.packed[pf * kSliceF4 + R.tid + i * kThreads];
-    }
-    if constexpr (!(V & ABL_BARRIER)) __syncthreads();
+    for (int i = 0; i < kStageF4; ++i) R.st[i] = R.packed[pf * kSliceF4 + R.tid + i * kThreads];
+    __syncthreads();
     ++R.it;
 }
 
@@ -530,10 +466,8 @@ __device__ __forceinline__ void pin(float &x) { asm volatile("" : "+v"(x)); }
 
 // One tile of a FiLM activation, in place: x = sin(gamma*x + beta) with the
 // reference's two roundings (sdf_model.py:67).
-template <int V>
 __device__ __forceinline__ void film_tile(f4 &x, const float *gam, const float *bet, int t,
                                           uint32_t g) {
-    if constexpr ((V & ABL_ACT) != 0) return;
     const f4 gm = *reinterpret_cast<const f4 *>(gam + 16 * t + 4 * g);
     const f4 bt = *reinterpret_cast<const f4 *>(bet + 16 * t + 4 * g);
     x.x = kSin(__fadd_rn(__fmul_rn(gm.x, x.x), bt.x));
@@ -577,7 +511,6 @@ __device__ __forceinline__ float dot_feat(const f4 (&act)[16], const float *w, u
     return group_sum(p);
 }
 
-template <int V>
 __global__ void __launch_bounds__(kThreads, 1) ngp_field_kernel(const FieldArgs a) {
     __shared__ f4 ring_lds[3 * kSliceF4];   // 48 KB weight ring
     __shared__ float cst[kCst];              // 9 KB biases + sigma/rgb rows
@@ -675,7 +608,7 @@ __global__ void __launch_bounds__(kThreads, 1) ngp_field_kernel(const FieldArgs 
         // their use as B operands, inside the MFMA stream.
         // layer 0: input_linear (32 -> 256), identity LinearLayer -> X
         init_bias(X, bias_l, g);
-        ring_step<V>(R, X, in_lo, [&] {
+        ring_step(R, X, in_lo, [&] {
             if (s + 1 < G.N) {                        // prefetch the next sample's features
                 sid += kTileRays;
                 e0 = enc2[(2 * g) * (size_t)G.S_total + sid];
@@ -684,38 +617,38 @@ __global__ void __launch_bounds__(kThreads, 1) ngp_field_kernel(const FieldArgs 
                 e3 = enc2[(9 + 2 * g) * (size_t)G.S_total + sid];
             }
         });
-        ring_step<V>(R, X, in_hi, NoSide{});
+        ring_step(R, X, in_hi, NoSide{});
         // layer 1: FiLM pts_linears.0 -> Y
         init_bias(Y, bias_l + kW, g);
 #pragma unroll
         for (int t = 0; t < 16; ++t)
-            ring_step<V>(R, Y, X[t], [&] {
-                if (t == 15) film_tile<V>(Y[0], f0g, f0b, 0, g);
+            ring_step(R, Y, X[t], [&] {
+                if (t == 15) film_tile(Y[0], f0g, f0b, 0, g);
             });
         // layer 2: FiLM pts_linears.1 -> X
         init_bias(X, bias_l + 2 * kW, g);
 #pragma unroll
         for (int t = 0; t < 16; ++t)
-            ring_step<V>(R, X, Y[t], [&] {
-                if (t < 15) film_tile<V>(Y[t + 1], f0g, f0b, t + 1, g);
-                else film_tile<V>(X[0], f1g, f1b, 0, g);
+            ring_step(R, X, Y[t], [&] {
+                if (t < 15) film_tile(Y[t + 1], f0g, f0b, t + 1, g);
+                else film_tile(X[0], f1g, f1b, 0, g);
             });
         // layer 3: FiLM pts_linears.2 -> Y
         init_bias(Y, bias_l + 3 * kW, g);
 #pragma unroll
         for (int t = 0; t < 16; ++t)
-            ring_step<V>(R, Y, X[t], [&] {
-                if (t < 15) film_tile<V>(X[t + 1], f1g, f1b, t + 1, g);
-                else film_tile<V>(Y[0], f2g, f2b, 0, g);
+            ring_step(R, Y, X[t], [&] {
+                if (t < 15) film_tile(X[t + 1], f1g, f1b, t + 1, g);
+                else film_tile(Y[0], f2g, f2b, 0, g);
             });
         // layer 4: views FiLM ([h3, SH] 272 -> 256) -> X; sigma_linear and the
         // sample's compositing weight ride in the last h3 slice
         init_bias(X, bias_l + 4 * kW, g);
 #pragma unroll
         for (int t = 0; t < 16; ++t)
-            ring_step<V>(R, X, Y[t], [&] {
+            ring_step(R, X, Y[t], [&] {
                 if (t < 15) {
-                    film_tile<V>(Y[t + 1], f2g, f2b, t + 1, g);
+                    film_tile(Y[t + 1], f2g, f2b, t + 1, g);
                 } else {
                     sdf = __fadd_rn(dot_feat(Y, sig_w, g), sig_b);
                     // volume_integration (sdf_model.py:236-301), front to back
@@ -737,10 +670,10 @@ __global__ void __launch_bounds__(kThreads, 1) ngp_field_kernel(const FieldArgs 
                     wsum += w;
                 }
             });
-        ring_step<V>(R, X, shq, NoSide{});
+        ring_step(R, X, shq, NoSide{});
         // colour features f = sin(gamma_v * . + beta_v); rgb_linear; compositing
 #pragma unroll
-        for (int t = 0; t < 16; ++t) film_tile<V>(X[t], f3g, f3b, t, g);
+        for (int t = 0; t < 16; ++t) film_tile(X[t], f3g, f3b, t, g);
         const float r0 = __fadd_rn(dot_feat(X, rgb_w, g), rgb_b0);
         const float r1 = __fadd_rn(dot_feat(X, rgb_w + kW, g), rgb_b1);
         const float r2 = __fadd_rn(dot_feat(X, rgb_w + 2 * kW, g), rgb_b2);
@@ -799,34 +732,6 @@ __global__ void __launch_bounds__(kThreads, 1) ngp_field_kernel(const FieldArgs 
 // host side: the launches of this unit's kernels (declared in render_launch.h; the render
 // entry points that call them are in render_api.hip)
 // ----------------------------------------------------------------------------
-#ifdef SDFR_ABLATION
-static int g_field_variant = 0;   // profiling ablations only (see ABL_*)
-static int field_variant() { return g_field_variant; }
-#else
-static int field_variant() { return 0; }
-#endif
-
-static void launch_field(int v, dim3 grid, hipStream_t st, const FieldArgs &f) {
-    switch (v) {
-#ifdef SDFR_ABLATION
-#define SDFR_FIELD_CASE(V)                                                                   \
-    case V:                                                                                  \
-        hipLaunchKernelGGL(ngp_field_kernel<V>, grid, dim3(kThreads), 0, st, f);             \
-        return;
-        SDFR_FIELD_CASE(1)
-        SDFR_FIELD_CASE(2)
-        SDFR_FIELD_CASE(4)
-        SDFR_FIELD_CASE(8)
-        SDFR_FIELD_CASE(15)
-        SDFR_FIELD_CASE(16)
-        SDFR_FIELD_CASE(31)
-#undef SDFR_FIELD_CASE
-#endif
-        default:
-            hipLaunchKernelGGL(ngp_field_kernel<0>, grid, dim3(kThreads), 0, st, f);
-    }
-}
-
 int launch_prep(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, f4 *packed, float *film,
                 hipStream_t st) {
     PrepArgs p;
@@ -855,20 +760,6 @@ int launch_prep(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, f4 *pa
     return check_launch("render_ngp: prep");
 }
 
-#ifdef SDFR_ABLATION
-static uint32_t g_encode_mode = [] {
-    const char *e = std::getenv("SDFR_ENC_MODE");   // ablations only
-    return e ? (uint32_t)std::atoi(e) : kEncDefault;
-}();
-#endif
-
-template <bool PAIR, bool A8, uint32_t LPT, uint32_t SPT>
-static void launch_encode_mode(hipStream_t st, const EncodeArgs &e) {
-    const uint32_t blocks = (e.g.S_total + 256 * SPT - 1) / (256 * SPT);
-    hipLaunchKernelGGL((ngp_encode_kernel<PAIR, A8, LPT, SPT>), dim3(blocks, 16 / LPT),
-                       dim3(256), 0, st, e);
-}
-
 // the per-sample geometry (sample_geom_kernel: gu always, zd when wanted)
 int launch_geom(const GeomArgs &g, float2 *zd, f4 *gu, hipStream_t st) {
     // samples per thread: all N, split while fewer than 64 k threads would run
@@ -891,22 +782,8 @@ int launch_encode(const sdfr_ngp_weights *w, const GeomArgs &g, float *enc, cons
     e.enc = enc;
     e.pair_ok = (reinterpret_cast<uintptr_t>(w->embeddings) & 15u) == 0;
     make_level_table(16, w->log2_per_level_scale, w->base_resolution, e.lt);
-#ifdef SDFR_ABLATION
-    switch (g_encode_mode) {
-        case 8 | 1: launch_encode_mode<false, false, 1, 1>(st, e); break;
-        case 1: launch_encode_mode<true, false, 1, 1>(st, e); break;
-        case 2: launch_encode_mode<true, false, 2, 1>(st, e); break;
-        case 32 | 1: launch_encode_mode<true, false, 1, 2>(st, e); break;
-        case 256 | 1: launch_encode_mode<true, true, 1, 1>(st, e); break;
-        case 256 | 2: launch_encode_mode<true, true, 2, 1>(st, e); break;
-        case 256 | 32 | 2: launch_encode_mode<true, true, 2, 2>(st, e); break;
-        case 256 | 32 | 1: launch_encode_mode<true, true, 1, 2>(st, e); break;
-        default: launch_encode_mode<true, true, 1, 1>(st, e); break;   // 257
-    }
-#else
-    static_assert(kEncDefault == (256 | 1), "product gather: A8, 1 level, 1 sample per thread");
-    launch_encode_mode<true, true, 1, 1>(st, e);
-#endif
+    hipLaunchKernelGGL((ngp_encode_kernel<1, 1>), dim3((g.S_total + 255) / 256, 16), dim3(256), 0,
+                       st, e);
     return check_launch("render_ngp: encode");
 }
 
@@ -937,7 +814,7 @@ int launch_field_fp32(const sdfr_ngp_weights *w, const sdfr_ngp_render_args *a, 
     f.xyz = a->xyz;
     f.mask = a->mask;
     const uint32_t blocks = (g.total_tiles + kWaves - 1) / kWaves;
-    launch_field(field_variant(), dim3(blocks), st, f);
+    hipLaunchKernelGGL(ngp_field_kernel, dim3(blocks), dim3(kThreads), 0, st, f);
     return check_launch("render_ngp: field");
 }
 
@@ -973,29 +850,4 @@ int sdfr_camera_extrinsics(const float *azim, const float *elev, uint32_t B, flo
                                fov_ang, half_res, B});
     return check_launch("camera_extrinsics");
 }
-
-#ifdef SDFR_ABLATION
-// profiling hooks (make ABLATION=1 builds only; process-global)
-int sdfr_debug_set_encode_mode(int mode) {
-    const int ok[] = {1, 2, 9, 33, 257, 258, 289, 290};
-    bool found = false;
-    for (int m : ok) found |= m == mode;
-    if (!found)
-        return fail(SDFR_EINVAL,
-                    "sdfr_debug_set_encode_mode: unknown mode");
-    g_encode_mode = (uint32_t)mode;
-    return SDFR_OK;
-}
-
-int sdfr_debug_set_field_variant(int variant) {
-    const int ok[] = {0, 1, 2, 4, 8, 15, 16, 31};
-    for (int v : ok)
-        if (v == variant) {
-            g_field_variant = variant;
-            return SDFR_OK;
-        }
-    return fail(SDFR_EINVAL,
-                "sdfr_debug_set_field_variant: variant must be 0,1,2,4,8,15,16,31");
-}
-#endif
 }  // extern "C"

@@ -14,15 +14,9 @@ from tests.golden import weights as W
 REPO = Path(__file__).resolve().parents[1]
 
 
-def header_symbols(ablation=False):
-    """Functions include/sdfr.h declares: the product ones, or (ablation=True) only
-    those of its `#ifdef SDFR_ABLATION` block (profiling builds)."""
+def header_symbols():
+    """Functions include/sdfr.h declares."""
     txt = (REPO / "include" / "sdfr.h").read_text()
-    blocks = re.findall(r"#ifdef SDFR_ABLATION\n(.*?)#endif", txt, re.S)
-    if ablation:
-        txt = "\n".join(blocks)
-    else:
-        txt = re.sub(r"#ifdef SDFR_ABLATION\n.*?#endif", "", txt, flags=re.S)
     return sorted(set(re.findall(r"^\s*(?:int|size_t|const char \*)\s*(sdfr_\w+)\s*\(", txt, re.M)))
 
 
@@ -42,12 +36,18 @@ def test_library_exports_every_header_symbol(sdfr):
         assert hasattr(lib, s), s
     assert set(syms) == set(sdfr._lib.EXPORTS)
     assert lib.sdfr_abi_version() == sdfr._lib.ABI_VERSION
-    # the product library exports exactly the documented entry points: no profiling
-    # hooks (process-global state) outside `make ABLATION=1` builds
-    assert library_symbols(sdfr._lib.LIB_PATH) == syms
-    assert header_symbols(ablation=True) == sorted(sdfr._lib.ABLATION_EXPORTS)
-    for s in sdfr._lib.ABLATION_EXPORTS:
-        assert not hasattr(lib, s), s
+    # the library exports exactly the documented entry points
+    exported = library_symbols(sdfr._lib.LIB_PATH)
+    assert exported == syms
+    # There is one build.  The header declares nothing under a build macro (its only
+    # conditionals are the include guard and the C++ linkage block; the profiling-build
+    # block it had up to commit a4b3009 is gone), and no debug setter that selects a
+    # kernel variant through process-global state is declared or exported.
+    header = (REPO / "include" / "sdfr.h").read_text()
+    conds = re.findall(r"^\s*#\s*(?:ifdef|ifndef|if|elif)\s+(.*)$", header, re.M)
+    assert sorted(conds) == ["SDFR_H_", "__cplusplus", "__cplusplus"]
+    for s in exported + syms:
+        assert not s.startswith("sdfr_debug_set_"), s
 
 
 def test_argument_errors_mirror_reference(sdfr):
