@@ -295,20 +295,24 @@ int sdfr_render_ngp_encode_only(const sdfr_ngp_weights *w,
  * sdfr_query_ngp_workspace_bytes(B, R, N) (about 144 bytes per point of the padded
  * count B ceil(R/16) 16 N) or 2^25 or more padded points in one call.
  * ------------------------------------------------------------------------- */
-typedef struct sdfr_ngp_query_args {
+/* One argument struct for the three networks' query calls; sdfr_{ngp,siren,fc}_query_args
+ * name it per network (the SIREN and FC calls' comments below say what differs). */
+typedef struct sdfr_query_args {
     uint32_t B, R, N;        /* faces; direction groups per face; points per group      */
-    const float *points;     /* [B,R,N,3] NETWORK coordinates: what NGPSIRENGenerator    */
+    const float *points;     /* [B,R,N,3] NETWORK coordinates: what the network's        */
                              /* .forward receives (normalized_pts, sdf_model.py:349);    */
-                             /* the grid coordinate u = (p + bound) / (2 bound) is formed */
-                             /* inside with the rounded ops of grid.py:149                */
+                             /* ngp: the grid coordinate u = (p + bound) / (2 bound) is   */
+                             /* formed inside with the rounded ops of grid.py:149         */
     const float *dirs;       /* [B,R,3] view direction of each group AS THE NETWORK SEES  */
                              /* IT (already unit length; not normalised again)            */
     const float *styles;     /* [B,256] renderer latent                                   */
     float *sdf;              /* [B,R,N]   sigma_linear output           (required)        */
     float *rgb;              /* [B,R,N,3] sigmoid(rgb_linear) in [0,1], or NULL           */
     void *workspace; size_t workspace_bytes;
-    const void *prepacked;   /* as sdfr_ngp_render_args.prepacked, or NULL                */
-} sdfr_ngp_query_args;
+    const void *prepacked;   /* as sdfr_ngp_render_args.prepacked (the network's own      */
+                             /* sdfr_render_*_pack buffer), or NULL                       */
+} sdfr_query_args;
+typedef sdfr_query_args sdfr_ngp_query_args;
 size_t sdfr_query_ngp_workspace_bytes(uint32_t B, uint32_t R, uint32_t N);
 int sdfr_query_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_query_args *a, void *stream);
 
@@ -334,15 +338,18 @@ int sdfr_query_ngp_forward(const sdfr_ngp_weights *w, const sdfr_ngp_query_args 
  * 32-bit arithmetic; sdfr_query_ngp_grad_workspace_bytes returns 0 for such a size);
  * SDFR_EUNSUPPORTED for num_levels != 16.
  * ------------------------------------------------------------------------- */
-typedef struct sdfr_ngp_grad_args {
+/* One argument struct for the three networks' gradient calls, named per network. */
+typedef struct sdfr_grad_args {
     uint32_t B, M;            /* faces; points per face                        */
     const float *points;      /* [B,M,3] network coordinates                   */
     const float *styles;      /* [B,256]                                       */
     float *sdf;               /* [B,M] or NULL                                 */
     float *grad;              /* [B,M,3] d sdf / d point (network coordinates) */
     void *workspace; size_t workspace_bytes;
-    const void *prepacked;    /* as sdfr_ngp_query_args.prepacked, or NULL     */
-} sdfr_ngp_grad_args;
+    const void *prepacked;    /* as sdfr_query_args.prepacked, or NULL (SIREN: */
+                              /* sdfr_query_siren_grad_pack's buffer)          */
+} sdfr_grad_args;
+typedef sdfr_grad_args sdfr_ngp_grad_args;
 size_t sdfr_query_ngp_grad_workspace_bytes(uint32_t B, uint32_t M);
 int sdfr_query_ngp_grad(const sdfr_ngp_weights *w, const sdfr_ngp_grad_args *a, void *stream);
 
@@ -421,17 +428,7 @@ int sdfr_render_ngp_geometry(const sdfr_ngp_weights *w, const sdfr_ngp_geometry_
  * size, and for products that wrap); SDFR_EUNSUPPORTED for depth != 8 or width != 256.
  * Asynchronous on `stream`; allocates nothing.
  * ------------------------------------------------------------------------- */
-typedef struct sdfr_siren_query_args {
-    uint32_t B, R, N;        /* faces; direction groups per face; points per group  */
-    const float *points;     /* [B,R,N,3] network coordinates                        */
-    const float *dirs;       /* [B,R,3] direction of each group as the network sees  */
-                             /* it (not normalised again)                            */
-    const float *styles;     /* [B,256] renderer latent                              */
-    float *sdf;              /* [B,R,N]   sigma_linear output           (required)   */
-    float *rgb;              /* [B,R,N,3] sigmoid(rgb_linear) in [0,1], or NULL      */
-    void *workspace; size_t workspace_bytes;
-    const void *prepacked;   /* sdfr_render_siren_pack's buffer, or NULL             */
-} sdfr_siren_query_args;
+typedef sdfr_query_args sdfr_siren_query_args; /* prepacked: sdfr_render_siren_pack's */
 size_t sdfr_query_siren_workspace_bytes(uint32_t B, uint32_t R, uint32_t N);
 int sdfr_query_siren_forward(const sdfr_siren_weights *w, const sdfr_siren_query_args *a,
                              void *stream);
@@ -466,15 +463,7 @@ int sdfr_query_siren_forward(const sdfr_siren_weights *w, const sdfr_siren_query
  * B x (M rounded up to 8) in one call (the size function returns 0 for such a size);
  * SDFR_EUNSUPPORTED for depth != 8 or width != 256.  Asynchronous; allocates nothing.
  * ------------------------------------------------------------------------- */
-typedef struct sdfr_siren_grad_args {
-    uint32_t B, M;            /* faces; points per face                        */
-    const float *points;      /* [B,M,3] network coordinates                   */
-    const float *styles;      /* [B,256]                                       */
-    float *sdf;               /* [B,M] or NULL                                 */
-    float *grad;              /* [B,M,3] d sdf / d point (network coordinates) */
-    void *workspace; size_t workspace_bytes;
-    const void *prepacked;    /* sdfr_query_siren_grad_pack's buffer, or NULL  */
-} sdfr_siren_grad_args;
+typedef sdfr_grad_args sdfr_siren_grad_args; /* prepacked: sdfr_query_siren_grad_pack's */
 size_t sdfr_query_siren_grad_workspace_bytes(uint32_t B, uint32_t M);
 size_t sdfr_query_siren_grad_pack_bytes(void);
 int sdfr_query_siren_grad_pack(const sdfr_siren_weights *w, void *packed, void *stream);
@@ -511,17 +500,7 @@ int sdfr_query_siren_grad(const sdfr_siren_weights *w, const sdfr_siren_grad_arg
  * products that wrap); SDFR_EUNSUPPORTED for depth != 8 or width != 256.
  * Asynchronous on `stream`; allocates nothing.
  * ------------------------------------------------------------------------- */
-typedef struct sdfr_fc_query_args {
-    uint32_t B, R, N;        /* faces; direction groups per face; points per group  */
-    const float *points;     /* [B,R,N,3] network coordinates                        */
-    const float *dirs;       /* [B,R,3] direction of each group as the network sees  */
-                             /* it (not normalised again)                            */
-    const float *styles;     /* [B,256] renderer latent                              */
-    float *sdf;              /* [B,R,N]   sigma_linear output           (required)   */
-    float *rgb;              /* [B,R,N,3] sigmoid(rgb_linear) in [0,1], or NULL      */
-    void *workspace; size_t workspace_bytes;
-    const void *prepacked;   /* sdfr_render_fc_pack's buffer, or NULL                */
-} sdfr_fc_query_args;
+typedef sdfr_query_args sdfr_fc_query_args;  /* prepacked: sdfr_render_fc_pack's buffer */
 size_t sdfr_query_fc_workspace_bytes(uint32_t B, uint32_t R, uint32_t N);
 int sdfr_query_fc_forward(const sdfr_fc_weights *w, const sdfr_fc_query_args *a, void *stream);
 
@@ -555,15 +534,7 @@ int sdfr_query_fc_forward(const sdfr_fc_weights *w, const sdfr_fc_query_args *a,
  * size function returns 0 for such a size); SDFR_EUNSUPPORTED for depth != 8 or
  * width != 256.  Asynchronous; allocates nothing.
  * ------------------------------------------------------------------------- */
-typedef struct sdfr_fc_grad_args {
-    uint32_t B, M;            /* faces; points per face                        */
-    const float *points;      /* [B,M,3] network coordinates                   */
-    const float *styles;      /* [B,256]                                       */
-    float *sdf;               /* [B,M] or NULL                                 */
-    float *grad;              /* [B,M,3] d sdf / d point (network coordinates) */
-    void *workspace; size_t workspace_bytes;
-    const void *prepacked;    /* sdfr_render_fc_pack's buffer, or NULL         */
-} sdfr_fc_grad_args;
+typedef sdfr_grad_args sdfr_fc_grad_args;    /* prepacked: sdfr_render_fc_pack's buffer */
 size_t sdfr_query_fc_grad_workspace_bytes(uint32_t B, uint32_t M);
 int sdfr_query_fc_grad(const sdfr_fc_weights *w, const sdfr_fc_grad_args *a, void *stream);
 

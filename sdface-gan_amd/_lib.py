@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections import namedtuple
 from pathlib import Path
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -27,49 +28,8 @@ ABI_VERSION = 15
 FIELD_F16X3 = 0
 FIELD_FP32 = 1
 
-# every symbol include/sdfr.h declares (tests check the .so exports all of them and
-# nothing else with the sdfr_ prefix)
-EXPORTS = (
-    "sdfr_abi_version", "sdfr_last_error",
-    "sdfr_grid_encode_forward", "sdfr_grid_encode_backward",
-    "sdfr_grid_encode_backward_ws_bytes", "sdfr_grid_encode_backward_ws",
-    "sdfr_sh_encode_forward", "sdfr_sh_encode_backward",
-    "sdfr_render_ngp_workspace_bytes", "sdfr_render_ngp_forward",
-    "sdfr_render_ngp_encode_only", "sdfr_query_ngp_workspace_bytes", "sdfr_query_ngp_forward",
-    "sdfr_query_ngp_grad_workspace_bytes", "sdfr_query_ngp_grad",
-    "sdfr_render_ngp_geometry_workspace_bytes", "sdfr_render_ngp_geometry",
-    "sdfr_render_ngp_surface_workspace_bytes", "sdfr_render_ngp_surface",
-    "sdfr_render_siren_surface_workspace_bytes", "sdfr_render_siren_surface",
-    "sdfr_query_siren_workspace_bytes", "sdfr_query_siren_forward",
-    "sdfr_query_siren_grad_workspace_bytes", "sdfr_query_siren_grad_pack_bytes",
-    "sdfr_query_siren_grad_pack", "sdfr_query_siren_grad",
-    "sdfr_debug_sin_probe",
-    "sdfr_debug_sin_rev_probe", "sdfr_camera_extrinsics",
-    "sdfr_render_siren_workspace_bytes", "sdfr_render_siren_forward",
-    "sdfr_render_pack_bytes", "sdfr_render_ngp_pack", "sdfr_render_siren_pack",
-    "sdfr_render_fc_workspace_bytes", "sdfr_render_fc_forward", "sdfr_render_fc_pack",
-    "sdfr_query_fc_workspace_bytes", "sdfr_query_fc_forward",
-    "sdfr_query_fc_grad_workspace_bytes", "sdfr_query_fc_grad",
-    "sdfr_fused_bias_act", "sdfr_mapping_linear", "sdfr_decoder_styles", "sdfr_upfirdn2d", "sdfr_styled_epilogue", "sdfr_modulate_to_nhwc",
-    "sdfr_modulate_to_nhwc_split",
-    "sdfr_conv_pack_bytes", "sdfr_conv_pack_weights", "sdfr_conv3x3_f16x3",
-    "sdfr_conv3x3_f16x3_ws", "sdfr_conv_ws_bytes", "sdfr_set_conv_t_mode",
-    "sdfr_conv3x3_f16x3_act", "sdfr_conv_act_ws_bytes", "sdfr_rgb_finish",
-    "sdfr_conv_t_act", "sdfr_conv_t_act_supported", "sdfr_conv_plan",
-    "sdfr_mc_workspace_bytes", "sdfr_mc_count", "sdfr_mc_emit",
-    "sdfr_brick_layout_workspace_bytes", "sdfr_brick_layout", "sdfr_brick_points",
-    "sdfr_mc_sparse_workspace_bytes", "sdfr_mc_sparse_count", "sdfr_mc_sparse_emit",
-    "sdfr_mesh_raster_workspace_bytes", "sdfr_mesh_raster", "sdfr_mesh_interpolate",
-    "sdfr_linear_pack_bytes", "sdfr_linear_pack", "sdfr_linear_f16x3",
-    "sdfr_linear_wgrad_ws_bytes", "sdfr_linear_wgrad_f16x3",
-    "sdfr_film_linear_f16x3", "sdfr_film_backward_ws_bytes", "sdfr_film_backward",
-    "sdfr_film_backward_grad_ws_bytes", "sdfr_film_backward_grad",
-    "sdfr_linear_head_forward", "sdfr_linear_head_ws_bytes", "sdfr_linear_head_backward",
-)
-
-
 class NgpWeights(ctypes.Structure):
-    """sdfr_ngp_weights (include/sdfr.h)."""
+    c_name = "sdfr_ngp_weights"
     _fields_ = [
         ("embeddings", _vp), ("offsets", _vp), ("num_levels", _u32),
         ("log2_per_level_scale", _f32), ("base_resolution", _u32), ("bound", _f32),
@@ -84,7 +44,7 @@ class NgpWeights(ctypes.Structure):
 
 
 class SirenWeights(ctypes.Structure):
-    """sdfr_siren_weights (include/sdfr.h)."""
+    c_name = "sdfr_siren_weights"
     _fields_ = [
         ("depth", _u32), ("width", _u32),
         ("pts_w", _vp * 8), ("pts_b", _vp * 8), ("pts_gw", _vp * 8), ("pts_gb", _vp * 8),
@@ -97,7 +57,7 @@ class SirenWeights(ctypes.Structure):
 
 
 class FcWeights(ctypes.Structure):
-    """sdfr_fc_weights (include/sdfr.h)."""
+    c_name = "sdfr_fc_weights"
     _fields_ = [
         ("depth", _u32), ("width", _u32),
         ("x_in_w", _vp), ("x_in_b", _vp), ("style_w", _vp), ("style_b", _vp),
@@ -109,7 +69,7 @@ class FcWeights(ctypes.Structure):
 
 
 class NgpRenderArgs(ctypes.Structure):
-    """sdfr_ngp_render_args (include/sdfr.h)."""
+    c_name = "sdfr_ngp_render_args"
     _fields_ = [
         ("B", _u32), ("H", _u32), ("W", _u32), ("N", _u32),
         ("cam", _vp), ("focal", _vp), ("near_", _vp), ("far_", _vp), ("styles", _vp),
@@ -125,8 +85,8 @@ class NgpRenderArgs(ctypes.Structure):
     ]
 
 
-class NgpQueryArgs(ctypes.Structure):
-    """sdfr_ngp_query_args (include/sdfr.h, ABI 14)."""
+class QueryArgs(ctypes.Structure):
+    c_name = "sdfr_query_args"
     _fields_ = [
         ("B", _u32), ("R", _u32), ("N", _u32),
         ("points", _vp), ("dirs", _vp), ("styles", _vp), ("sdf", _vp), ("rgb", _vp),
@@ -134,8 +94,8 @@ class NgpQueryArgs(ctypes.Structure):
     ]
 
 
-class NgpGradArgs(ctypes.Structure):
-    """sdfr_ngp_grad_args (include/sdfr.h, ABI 15)."""
+class GradArgs(ctypes.Structure):
+    c_name = "sdfr_grad_args"
     _fields_ = [
         ("B", _u32), ("M", _u32),
         ("points", _vp), ("styles", _vp), ("sdf", _vp), ("grad", _vp),
@@ -143,28 +103,14 @@ class NgpGradArgs(ctypes.Structure):
     ]
 
 
-class SirenQueryArgs(ctypes.Structure):
-    """sdfr_siren_query_args (include/sdfr.h)."""
-    _fields_ = list(NgpQueryArgs._fields_)
-
-
-class SirenGradArgs(ctypes.Structure):
-    """sdfr_siren_grad_args (include/sdfr.h)."""
-    _fields_ = list(NgpGradArgs._fields_)
-
-
-class FcQueryArgs(ctypes.Structure):
-    """sdfr_fc_query_args (include/sdfr.h)."""
-    _fields_ = list(NgpQueryArgs._fields_)
-
-
-class FcGradArgs(ctypes.Structure):
-    """sdfr_fc_grad_args (include/sdfr.h)."""
-    _fields_ = list(NgpGradArgs._fields_)
+# the three networks' query / gradient calls take one struct each; the per-network names of
+# the header's typedefs stay as aliases
+NgpQueryArgs = SirenQueryArgs = FcQueryArgs = QueryArgs
+NgpGradArgs = SirenGradArgs = FcGradArgs = GradArgs
 
 
 class NgpGeometryArgs(ctypes.Structure):
-    """sdfr_ngp_geometry_args (include/sdfr.h)."""
+    c_name = "sdfr_ngp_geometry_args"
     _fields_ = [
         ("B", _u32), ("H", _u32), ("W", _u32), ("N", _u32),
         ("cam", _vp), ("focal", _vp), ("near_", _vp), ("far_", _vp), ("styles", _vp),
@@ -178,7 +124,7 @@ class NgpGeometryArgs(ctypes.Structure):
 
 
 class SurfaceArgs(ctypes.Structure):
-    """sdfr_surface_args (include/sdfr.h)."""
+    c_name = "sdfr_surface_args"
     _fields_ = [
         ("B", _u32), ("H", _u32), ("W", _u32), ("N", _u32),
         ("cam", _vp), ("focal", _vp), ("near_", _vp), ("far_", _vp), ("styles", _vp),
@@ -193,7 +139,7 @@ class SurfaceArgs(ctypes.Structure):
 
 
 class RasterArgs(ctypes.Structure):
-    """sdfr_raster_args (include/sdfr.h)."""
+    c_name = "sdfr_raster_args"
     _fields_ = [
         ("B", _u32), ("H", _u32), ("W", _u32), ("V", _u32), ("F", _u32),
         ("vertices", _vp), ("faces", _vp), ("cam", _vp), ("focal", _vp),
@@ -204,7 +150,7 @@ class RasterArgs(ctypes.Structure):
 
 
 class StyledEpilogueArgs(ctypes.Structure):
-    """sdfr_styled_epilogue_args (include/sdfr.h)."""
+    c_name = "sdfr_styled_epilogue_args"
     _fields_ = [
         ("B", _u32), ("C", _u32), ("H", _u32), ("W", _u32),
         ("conv", _vp), ("blur_up", _int), ("fir", _f32 * 4),
@@ -216,7 +162,7 @@ class StyledEpilogueArgs(ctypes.Structure):
 
 
 class StyleArgs(ctypes.Structure):
-    """sdfr_style_args (include/sdfr.h)."""
+    c_name = "sdfr_style_args"
     _fields_ = [
         ("B", _u32), ("n_latent", _u32), ("K", _u32), ("latent", _vp),
         ("L", _u32), ("cmax", _u32), ("mod_w", _vp), ("mod_b", _vp),
@@ -227,7 +173,7 @@ class StyleArgs(ctypes.Structure):
 
 
 class ConvActArgs(ctypes.Structure):
-    """sdfr_conv_act_args (include/sdfr.h)."""
+    c_name = "sdfr_conv_act_args"
     _fields_ = [
         ("x_split", _vp), ("packed", _vp),
         ("B", _u32), ("H", _u32), ("W", _u32), ("Cin", _u32), ("Cout", _u32),
@@ -240,7 +186,7 @@ class ConvActArgs(ctypes.Structure):
 
 
 class ConvTActArgs(ctypes.Structure):
-    """sdfr_conv_t_act_args (include/sdfr.h, ABI 13)."""
+    c_name = "sdfr_conv_t_act_args"
     _fields_ = [
         ("x_split", _vp), ("packed", _vp),
         ("B", _u32), ("H", _u32), ("W", _u32), ("Cin", _u32), ("Cout", _u32),
@@ -262,7 +208,7 @@ CONV_PLAN_KERNELS = (
 
 
 class ConvPlanQuery(ctypes.Structure):
-    """sdfr_conv_plan_query (include/sdfr.h)."""
+    c_name = "sdfr_conv_plan_query"
     _fields_ = [
         ("B", _u32), ("H", _u32), ("W", _u32), ("Cin", _u32), ("Cout", _u32),
         ("transposed", _int), ("epilogue", _int), ("has_ws", _int),
@@ -275,12 +221,137 @@ class ConvPlanStep(ctypes.Structure):
 
 
 class ConvPlanInfo(ctypes.Structure):
-    """sdfr_conv_plan_info (include/sdfr.h)."""
+    c_name = "sdfr_conv_plan_info"
     _fields_ = [
         ("rc", _int), ("ksplit", _u32), ("ksplit_t", _u32), ("ws_bytes", ctypes.c_size_t),
         ("nsteps", _u32), ("steps", ConvPlanStep * 6),
     ]
 
+
+# ---------------------------------------------------------------------------
+# The three renderer networks, each described once: the library's name for it (and its
+# index, the ``kind`` / ``net`` of the Python and C side), its weights struct, and the
+# struct's tensor members in the order of the flat tensor list that the registered op
+# sdfr::render_fused takes (render_calls.weights_struct fills the struct by zipping the
+# two).  sigmoid_beta is last (a placeholder tensor without an SDF).
+# ---------------------------------------------------------------------------
+Network = namedtuple("Network", ("name", "weights", "fields"))
+
+
+def _layers(n, members):
+    return tuple(f"pts_{m}[{l}]" for l in range(n) for m in members) + \
+        tuple(f"views_{m}" for m in members)
+
+
+_FILM = ("w", "b", "gw", "gb", "bw", "bb")      # a FiLM layer: w, b, gamma w, b, beta w, b
+_HEADS = ("sigma_w", "sigma_b", "rgb_w", "rgb_b", "sigmoid_beta")
+NETWORKS = (
+    Network("ngp", NgpWeights, ("embeddings", "offsets", "input_w", "input_b")
+            + _layers(3, _FILM) + _HEADS),
+    Network("siren", SirenWeights, _layers(8, _FILM) + _HEADS),
+    Network("fc", FcWeights, ("x_in_w", "x_in_b", "style_w", "style_b")
+            + _layers(7, ("w", "b")) + _HEADS),
+)
+
+# ---------------------------------------------------------------------------
+# Every function include/sdfr.h declares: name -> (restype, argtypes).  tests/test_abi.py
+# compares the table with the header's prototypes and the structs above with its layouts.
+# ---------------------------------------------------------------------------
+_P = ctypes.POINTER
+_sz = ctypes.c_size_t
+_i64 = ctypes.c_int64
+_GRID_BWD = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _u32, _int,
+             _u32]
+_MC = [_vp, _u32, _u32, _u32, _i64, _i64, _i64, _f32, _vp, _sz]
+_MC_SPARSE = [_vp, _vp, _vp, _u32, _u32, _f32, _vp, _sz, _vp]
+PROTOTYPES = {
+    "sdfr_abi_version": (_int, []),
+    "sdfr_last_error": (ctypes.c_char_p, []),
+    "sdfr_grid_encode_forward": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32,
+                                        _vp, _u32, _int, _u32, _vp]),
+    "sdfr_grid_encode_backward": (_int, _GRID_BWD + [_vp]),
+    "sdfr_grid_encode_backward_ws_bytes": (_sz, [_u32, _u32, _u32, _u32, _f32, _u32, _int]),
+    "sdfr_grid_encode_backward_ws": (_int, _GRID_BWD + [_vp, _sz, _vp]),
+    "sdfr_sh_encode_forward": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "sdfr_sh_encode_backward": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    # the three render workspaces depend on different sizes: prefixes of (B, H, W, N, levels)
+    "sdfr_render_ngp_workspace_bytes": (_sz, [_u32] * 5),
+    "sdfr_render_siren_workspace_bytes": (_sz, [_u32]),
+    "sdfr_render_fc_workspace_bytes": (_sz, [_u32] * 4),
+    "sdfr_render_pack_bytes": (_sz, [_int]),
+    "sdfr_render_ngp_encode_only": (_int, [_P(NgpWeights), _P(NgpRenderArgs), _vp]),
+    "sdfr_render_ngp_geometry_workspace_bytes": (_sz, [_u32] * 4),
+    "sdfr_render_ngp_geometry": (_int, [_P(NgpWeights), _P(NgpGeometryArgs), _vp]),
+    "sdfr_query_siren_grad_pack_bytes": (_sz, []),
+    "sdfr_query_siren_grad_pack": (_int, [_P(SirenWeights), _vp, _vp]),
+    "sdfr_debug_sin_probe": (_int, [_vp, _vp, _vp, _u32, _vp]),
+    "sdfr_debug_sin_rev_probe": (_int, [_vp, _vp, _u32, _vp]),
+    "sdfr_camera_extrinsics": (_int, [_vp, _vp, _u32, _f32, _f32, _f32] + [_vp] * 6),
+    "sdfr_fused_bias_act": (_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _u32, _u32, _int, _int,
+                                   _f32, _f32, _vp]),
+    "sdfr_mapping_linear": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _int, _f32,
+                                   _f32, _int, _vp]),
+    "sdfr_decoder_styles": (_int, [_P(StyleArgs), _vp]),
+    "sdfr_upfirdn2d": (_int, [_vp, _vp, _vp] + [_u32] * 5 + [_int] * 8 + [_vp]),
+    "sdfr_styled_epilogue": (_int, [_P(StyledEpilogueArgs), _vp]),
+    "sdfr_modulate_to_nhwc": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp]),
+    "sdfr_modulate_to_nhwc_split": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp]),
+    "sdfr_conv_pack_bytes": (_sz, [_u32, _u32]),
+    "sdfr_conv_pack_weights": (_int, [_vp, _f32, _u32, _u32, _vp, _vp, _vp]),
+    "sdfr_conv3x3_f16x3": (_int, [_vp, _vp, _vp] + [_u32] * 5 + [_int, _vp]),
+    "sdfr_conv3x3_f16x3_ws": (_int, [_vp, _vp, _vp] + [_u32] * 5 + [_int, _vp, _sz, _vp]),
+    "sdfr_conv_ws_bytes": (_sz, [_u32, _u32, _u32, _u32, _int]),
+    "sdfr_set_conv_t_mode": (_int, [_int]),
+    "sdfr_conv3x3_f16x3_act": (_int, [_P(ConvActArgs), _vp]),
+    "sdfr_conv_t_act": (_int, [_P(ConvTActArgs), _vp]),
+    "sdfr_conv_t_act_supported": (_int, [_u32] * 5),
+    "sdfr_conv_act_ws_bytes": (_sz, [_u32] * 4),
+    "sdfr_conv_plan": (_int, [_P(ConvPlanQuery), _P(ConvPlanInfo)]),
+    "sdfr_rgb_finish": (_int, [_vp, _vp, _u32, _vp, _vp, _P(_f32), _u32, _u32, _u32, _vp]),
+    "sdfr_mc_workspace_bytes": (_sz, [_u32] * 3),
+    "sdfr_mc_count": (_int, _MC + [_P(_u32), _vp]),
+    "sdfr_mc_emit": (_int, _MC + [_vp, _vp, _vp]),
+    "sdfr_brick_layout_workspace_bytes": (_sz, [_u32]),
+    "sdfr_brick_layout": (_int, [_vp, _u32, _vp, _u32, _vp, _sz, _P(_u32), _vp]),
+    "sdfr_brick_points": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "sdfr_mc_sparse_workspace_bytes": (_sz, [_u32]),
+    "sdfr_mc_sparse_count": (_int, _MC_SPARSE + [_P(_u32), _vp]),
+    "sdfr_mc_sparse_emit": (_int, _MC_SPARSE + [_vp, _vp]),
+    "sdfr_mesh_raster_workspace_bytes": (_sz, [_u32] * 5),
+    "sdfr_mesh_raster": (_int, [_P(RasterArgs), _vp]),
+    "sdfr_mesh_interpolate": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32,
+                                     _vp, _u32, _f32, _vp, _vp]),
+    "sdfr_linear_pack_bytes": (_sz, [_u32, _u32]),
+    "sdfr_linear_pack": (_int, [_vp, _u32, _u32, _int, _vp, _vp]),
+    "sdfr_linear_f16x3": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp]),
+    "sdfr_linear_wgrad_ws_bytes": (_sz, [_u32] * 3),
+    "sdfr_linear_wgrad_f16x3": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _sz, _vp]),
+    "sdfr_film_linear_f16x3": (_int, [_vp] * 7 + [_u32] * 4 + [_vp]),
+    "sdfr_film_backward_ws_bytes": (_sz, [_u32] * 3),
+    "sdfr_film_backward": (_int, [_vp] * 8 + [_u32] * 3 + [_vp, _sz, _vp]),
+    "sdfr_film_backward_grad_ws_bytes": (_sz, [_u32] * 3),
+    "sdfr_film_backward_grad": (_int, [_vp] * 11 + [_u32] * 3 + [_vp, _sz, _vp]),
+    "sdfr_linear_head_forward": (_int, [_vp] * 4 + [_u32] * 3 + [_vp]),
+    "sdfr_linear_head_ws_bytes": (_sz, [_u32] * 3),
+    "sdfr_linear_head_backward": (_int, [_vp] * 6 + [_u32] * 3 + [_vp, _sz, _vp]),
+}
+for _n in NETWORKS:
+    _w = _P(_n.weights)
+    PROTOTYPES.update({
+        f"sdfr_render_{_n.name}_forward": (_int, [_w, _P(NgpRenderArgs), _vp]),
+        f"sdfr_render_{_n.name}_pack": (_int, [_w, _vp, _vp]),
+        f"sdfr_query_{_n.name}_workspace_bytes": (_sz, [_u32] * 3),
+        f"sdfr_query_{_n.name}_forward": (_int, [_w, _P(QueryArgs), _vp]),
+        f"sdfr_query_{_n.name}_grad_workspace_bytes": (_sz, [_u32] * 2),
+        f"sdfr_query_{_n.name}_grad": (_int, [_w, _P(GradArgs), _vp]),
+    })
+    if _n.name != "fc":                         # (FC has the point calls only)
+        PROTOTYPES.update({
+            f"sdfr_render_{_n.name}_surface_workspace_bytes": (_sz, [_u32] * 4),
+            f"sdfr_render_{_n.name}_surface": (_int, [_w, _P(SurfaceArgs), _vp]),
+        })
+# (tests check that the .so exports all of these and nothing else with the sdfr_ prefix)
+EXPORTS = tuple(PROTOTYPES)
 
 _lib = None
 
@@ -295,148 +366,9 @@ def lib():
             f"sdface-gan_amd: HIP library {LIB_PATH} is missing; build it with "
             "`make -C sdface-gan_amd` or `python -c 'import __graft_entry__ as g; g.build()'`")
     L = ctypes.CDLL(str(LIB_PATH))
-    L.sdfr_abi_version.restype = _int
-    L.sdfr_last_error.restype = ctypes.c_char_p
-    L.sdfr_grid_encode_forward.argtypes = [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32,
-                                           _u32, _vp, _u32, _int, _u32, _vp]
-    L.sdfr_grid_encode_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32,
-                                            _f32, _u32, _vp, _vp, _u32, _int, _u32, _vp]
-    L.sdfr_grid_encode_backward_ws_bytes.argtypes = [_u32, _u32, _u32, _u32, _f32, _u32, _int]
-    L.sdfr_grid_encode_backward_ws_bytes.restype = ctypes.c_size_t
-    L.sdfr_grid_encode_backward_ws.argtypes = (L.sdfr_grid_encode_backward.argtypes[:-1]
-                                               + [_vp, ctypes.c_size_t, _vp])
-    L.sdfr_sh_encode_forward.argtypes = [_vp, _vp, _u32, _u32, _u32, _vp, _vp]
-    L.sdfr_sh_encode_backward.argtypes = [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]
-    L.sdfr_render_ngp_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_render_ngp_workspace_bytes.argtypes = [_u32, _u32, _u32, _u32, _u32]
-    L.sdfr_render_ngp_forward.argtypes = [ctypes.POINTER(NgpWeights),
-                                          ctypes.POINTER(NgpRenderArgs), _vp]
-    L.sdfr_render_ngp_encode_only.argtypes = [ctypes.POINTER(NgpWeights),
-                                              ctypes.POINTER(NgpRenderArgs), _vp]
-    L.sdfr_query_ngp_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_query_ngp_workspace_bytes.argtypes = [_u32, _u32, _u32]
-    L.sdfr_query_ngp_forward.argtypes = [ctypes.POINTER(NgpWeights),
-                                         ctypes.POINTER(NgpQueryArgs), _vp]
-    L.sdfr_query_ngp_grad_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_query_ngp_grad_workspace_bytes.argtypes = [_u32, _u32]
-    L.sdfr_query_ngp_grad.argtypes = [ctypes.POINTER(NgpWeights),
-                                      ctypes.POINTER(NgpGradArgs), _vp]
-    L.sdfr_render_ngp_geometry_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_render_ngp_geometry_workspace_bytes.argtypes = [_u32, _u32, _u32, _u32]
-    L.sdfr_render_ngp_geometry.argtypes = [ctypes.POINTER(NgpWeights),
-                                           ctypes.POINTER(NgpGeometryArgs), _vp]
-    for net, weights in (("ngp", NgpWeights), ("siren", SirenWeights)):
-        size = getattr(L, f"sdfr_render_{net}_surface_workspace_bytes")
-        size.restype = ctypes.c_size_t
-        size.argtypes = [_u32, _u32, _u32, _u32]
-        getattr(L, f"sdfr_render_{net}_surface").argtypes = [
-            ctypes.POINTER(weights), ctypes.POINTER(SurfaceArgs), _vp]
-    L.sdfr_render_siren_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_render_siren_workspace_bytes.argtypes = [_u32]
-    L.sdfr_render_pack_bytes.argtypes = [_int]
-    L.sdfr_render_pack_bytes.restype = ctypes.c_size_t
-    L.sdfr_render_ngp_pack.argtypes = [ctypes.POINTER(NgpWeights), _vp, _vp]
-    L.sdfr_render_siren_pack.argtypes = [ctypes.POINTER(SirenWeights), _vp, _vp]
-    L.sdfr_render_siren_forward.argtypes = [ctypes.POINTER(SirenWeights),
-                                            ctypes.POINTER(NgpRenderArgs), _vp]
-    L.sdfr_query_siren_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_query_siren_workspace_bytes.argtypes = [_u32, _u32, _u32]
-    L.sdfr_query_siren_forward.argtypes = [ctypes.POINTER(SirenWeights),
-                                           ctypes.POINTER(SirenQueryArgs), _vp]
-    L.sdfr_query_siren_grad_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_query_siren_grad_workspace_bytes.argtypes = [_u32, _u32]
-    L.sdfr_query_siren_grad_pack_bytes.restype = ctypes.c_size_t
-    L.sdfr_query_siren_grad_pack_bytes.argtypes = []
-    L.sdfr_query_siren_grad_pack.argtypes = [ctypes.POINTER(SirenWeights), _vp, _vp]
-    L.sdfr_query_siren_grad.argtypes = [ctypes.POINTER(SirenWeights),
-                                        ctypes.POINTER(SirenGradArgs), _vp]
-    L.sdfr_render_fc_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_render_fc_workspace_bytes.argtypes = [_u32, _u32, _u32, _u32]
-    L.sdfr_render_fc_pack.argtypes = [ctypes.POINTER(FcWeights), _vp, _vp]
-    L.sdfr_render_fc_forward.argtypes = [ctypes.POINTER(FcWeights),
-                                         ctypes.POINTER(NgpRenderArgs), _vp]
-    L.sdfr_query_fc_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_query_fc_workspace_bytes.argtypes = [_u32, _u32, _u32]
-    L.sdfr_query_fc_forward.argtypes = [ctypes.POINTER(FcWeights),
-                                        ctypes.POINTER(FcQueryArgs), _vp]
-    L.sdfr_query_fc_grad_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_query_fc_grad_workspace_bytes.argtypes = [_u32, _u32]
-    L.sdfr_query_fc_grad.argtypes = [ctypes.POINTER(FcWeights),
-                                     ctypes.POINTER(FcGradArgs), _vp]
-    L.sdfr_debug_sin_probe.argtypes = [_vp, _vp, _vp, _u32, _vp]
-    L.sdfr_debug_sin_rev_probe.argtypes = [_vp, _vp, _u32, _vp]
-    L.sdfr_camera_extrinsics.argtypes = [_vp, _vp, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp,
-                                         _vp, _vp]
-    L.sdfr_fused_bias_act.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_uint64, _u32, _u32, _int, _int,
-                                      _f32, _f32, _vp]
-    L.sdfr_mapping_linear.argtypes = [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _int, _f32,
-                                      _f32, _int, _vp]
-    L.sdfr_decoder_styles.argtypes = [ctypes.POINTER(StyleArgs), _vp]
-    L.sdfr_upfirdn2d.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32] + [_int] * 8 + [_vp]
-    L.sdfr_styled_epilogue.argtypes = [ctypes.POINTER(StyledEpilogueArgs), _vp]
-    L.sdfr_modulate_to_nhwc.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _vp]
-    L.sdfr_modulate_to_nhwc_split.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _vp]
-    L.sdfr_conv_pack_bytes.restype = ctypes.c_size_t
-    L.sdfr_conv_pack_bytes.argtypes = [_u32, _u32]
-    L.sdfr_conv_pack_weights.argtypes = [_vp, _f32, _u32, _u32, _vp, _vp, _vp]
-    L.sdfr_conv3x3_f16x3.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _int, _vp]
-    L.sdfr_conv3x3_f16x3_ws.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _int, _vp,
-                                        ctypes.c_size_t, _vp]
-    L.sdfr_conv_ws_bytes.argtypes = [_u32, _u32, _u32, _u32, _int]
-    L.sdfr_conv_ws_bytes.restype = ctypes.c_size_t
-    L.sdfr_set_conv_t_mode.argtypes = [_int]
-    L.sdfr_set_conv_t_mode.restype = _int
-    L.sdfr_conv3x3_f16x3_act.argtypes = [ctypes.POINTER(ConvActArgs), _vp]
-    L.sdfr_conv_t_act.argtypes = [ctypes.POINTER(ConvTActArgs), _vp]
-    L.sdfr_conv_t_act_supported.argtypes = [_u32, _u32, _u32, _u32, _u32]
-    L.sdfr_conv_t_act_supported.restype = _int
-    L.sdfr_conv_act_ws_bytes.argtypes = [_u32, _u32, _u32, _u32]
-    L.sdfr_conv_act_ws_bytes.restype = ctypes.c_size_t
-    L.sdfr_conv_plan.argtypes = [ctypes.POINTER(ConvPlanQuery), ctypes.POINTER(ConvPlanInfo)]
-    _i64 = ctypes.c_int64
-    L.sdfr_mc_workspace_bytes.argtypes = [_u32, _u32, _u32]
-    L.sdfr_mc_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_mc_count.argtypes = [_vp, _u32, _u32, _u32, _i64, _i64, _i64, _f32, _vp,
-                                ctypes.c_size_t, ctypes.POINTER(_u32), _vp]
-    L.sdfr_mc_emit.argtypes = [_vp, _u32, _u32, _u32, _i64, _i64, _i64, _f32, _vp,
-                               ctypes.c_size_t, _vp, _vp, _vp]
-    L.sdfr_brick_layout_workspace_bytes.argtypes = [_u32]
-    L.sdfr_brick_layout_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_brick_layout.argtypes = [_vp, _u32, _vp, _u32, _vp, ctypes.c_size_t,
-                                    ctypes.POINTER(_u32), _vp]
-    L.sdfr_brick_points.argtypes = [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]
-    L.sdfr_mc_sparse_workspace_bytes.argtypes = [_u32]
-    L.sdfr_mc_sparse_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_mc_sparse_count.argtypes = [_vp, _vp, _vp, _u32, _u32, _f32, _vp, ctypes.c_size_t,
-                                       _vp, ctypes.POINTER(_u32), _vp]
-    L.sdfr_mc_sparse_emit.argtypes = [_vp, _vp, _vp, _u32, _u32, _f32, _vp, ctypes.c_size_t,
-                                      _vp, _vp, _vp]
-    L.sdfr_mesh_raster_workspace_bytes.argtypes = [_u32] * 5
-    L.sdfr_mesh_raster_workspace_bytes.restype = ctypes.c_size_t
-    L.sdfr_mesh_raster.argtypes = [ctypes.POINTER(RasterArgs), _vp]
-    L.sdfr_mesh_interpolate.argtypes = [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32,
-                                        _vp, _u32, _f32, _vp, _vp]
-    L.sdfr_rgb_finish.argtypes = [_vp, _vp, _u32, _vp, _vp, ctypes.POINTER(_f32), _u32, _u32,
-                                  _u32, _vp]
-    L.sdfr_linear_pack_bytes.argtypes = [_u32, _u32]
-    L.sdfr_linear_pack_bytes.restype = ctypes.c_size_t
-    L.sdfr_linear_pack.argtypes = [_vp, _u32, _u32, _int, _vp, _vp]
-    L.sdfr_linear_f16x3.argtypes = [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp]
-    L.sdfr_linear_wgrad_ws_bytes.argtypes = [_u32, _u32, _u32]
-    L.sdfr_linear_wgrad_ws_bytes.restype = ctypes.c_size_t
-    L.sdfr_linear_wgrad_f16x3.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _vp, ctypes.c_size_t,
-                                          _vp]
-    L.sdfr_film_linear_f16x3.argtypes = [_vp] * 7 + [_u32] * 4 + [_vp]
-    L.sdfr_film_backward_ws_bytes.argtypes = [_u32, _u32, _u32]
-    L.sdfr_film_backward_ws_bytes.restype = ctypes.c_size_t
-    L.sdfr_film_backward.argtypes = [_vp] * 8 + [_u32] * 3 + [_vp, ctypes.c_size_t, _vp]
-    L.sdfr_film_backward_grad_ws_bytes.argtypes = [_u32, _u32, _u32]
-    L.sdfr_film_backward_grad_ws_bytes.restype = ctypes.c_size_t
-    L.sdfr_film_backward_grad.argtypes = [_vp] * 11 + [_u32] * 3 + [_vp, ctypes.c_size_t, _vp]
-    L.sdfr_linear_head_forward.argtypes = [_vp] * 4 + [_u32] * 3 + [_vp]
-    L.sdfr_linear_head_ws_bytes.argtypes = [_u32, _u32, _u32]
-    L.sdfr_linear_head_ws_bytes.restype = ctypes.c_size_t
-    L.sdfr_linear_head_backward.argtypes = [_vp] * 6 + [_u32] * 3 + [_vp, ctypes.c_size_t, _vp]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     v = L.sdfr_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"libsdfr ABI {v} != expected {ABI_VERSION}; rebuild the library")

@@ -328,10 +328,9 @@ int check_fc_weights(const sdfr_fc_weights *w, const char *who) {
     return null ? err(who, SDFR_EINVAL, "weight pointer is null") : SDFR_OK;
 }
 
-// the sizes and pointers of a query / gradient call (the ngp and SIREN argument structs
-// have the same fields)
-template <class Weights, class Args>
-int check_query_args(const Weights *w, const Args *a, const char *who) {
+// the sizes and pointers of a query / gradient call (one argument struct for the three
+// networks)
+int check_query_args(const void *w, const sdfr_query_args *a, const char *who) {
     if (!w || !a) return err(who, SDFR_EINVAL, "null args");
     if (a->B == 0 || a->R == 0 || a->N == 0)
         return err(who, SDFR_EINVAL, "empty batch / group / point count");
@@ -340,8 +339,7 @@ int check_query_args(const Weights *w, const Args *a, const char *who) {
     return SDFR_OK;
 }
 
-template <class Weights, class Args>
-int check_grad_args(const Weights *w, const Args *a, const char *who) {
+int check_grad_args(const void *w, const sdfr_grad_args *a, const char *who) {
     if (!w || !a) return err(who, SDFR_EINVAL, "null args");
     if (a->B == 0 || a->M == 0) return err(who, SDFR_EINVAL, "empty batch / point count");
     if (any_null({a->points, a->styles, a->grad, a->workspace}))

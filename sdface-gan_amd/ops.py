@@ -24,19 +24,19 @@ shape propagation and ``torch.compile`` tracing; the drop-in modules call them
         -> (rgb[B,3,H,W], features[B,256,H,W] or [0], sdf[B,H,W,N,1] or [0],
             mask[B,1,H,W] or [0], xyz[B,3,H,W] or [0])
      (sdfr_render_{ngp,siren,fc}_forward: kind 0 / 1 / 2; ``params`` in the order of
-     ``weight_tensors``; ``flags`` = RENDER_FLAGS.)
+     ``_lib.NETWORKS[kind].fields``; ``flags`` = RENDER_FLAGS.)
 
 An absent optional output is a 0-element tensor (a custom op returns tensors only).
 """
 from __future__ import annotations
 
-import ctypes
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from . import _lib
+from .render_calls import render_args, render_forward, weights_struct, workspace_bytes
 
 RENDER_FLAGS = ("t_rand_per_sample", "offset_sampling", "static_viewdirs", "z_normalize",
                 "force_background", "with_sdf", "field_precision", "max_field_segments",
@@ -166,85 +166,6 @@ def _(grad, inputs, dy_dx, degree):
 
 
 # ---------------------------------------------------------------- fused render
-def weights_struct(kind: int, ts: Sequence[Tensor], fscal: Sequence[float],
-                   iscal: Sequence[int], with_sdf: bool):
-    """sdfr_{ngp,siren,fc}_weights from the flat tensor list of weight_tensors (kind 0 /
-    1 / 2) and the network's scalars (ngp: fscal = (log2 per-level scale, bound), iscal =
-    (base resolution,); SIREN / FC: iscal = (depth, width))."""
-    P = _lib.ptr
-    it = iter(ts)
-    nxt = lambda: P(next(it))  # noqa: E731
-    if kind == 0:
-        w = _lib.NgpWeights()
-        emb, off = next(it), next(it)
-        w.embeddings, w.offsets = P(emb), P(off)
-        w.num_levels = off.shape[0] - 1
-        w.log2_per_level_scale, w.bound = float(fscal[0]), float(fscal[1])
-        w.base_resolution = int(iscal[0])
-        w.input_w, w.input_b = nxt(), nxt()
-        n_pts = 3
-    elif kind == 1:
-        w = _lib.SirenWeights()
-        w.depth, w.width = int(iscal[0]), int(iscal[1])
-        n_pts = 8
-    else:
-        w = _lib.FcWeights()
-        w.depth, w.width = int(iscal[0]), int(iscal[1])
-        w.x_in_w, w.x_in_b, w.style_w, w.style_b = nxt(), nxt(), nxt(), nxt()
-        for l in range(7):
-            w.pts_w[l], w.pts_b[l] = nxt(), nxt()
-        w.views_w, w.views_b = nxt(), nxt()
-    if kind != 2:
-        for l in range(n_pts):
-            w.pts_w[l], w.pts_b[l] = nxt(), nxt()
-            w.pts_gw[l], w.pts_gb[l] = nxt(), nxt()
-            w.pts_bw[l], w.pts_bb[l] = nxt(), nxt()
-        w.views_w, w.views_b = nxt(), nxt()
-        w.views_gw, w.views_gb = nxt(), nxt()
-        w.views_bw, w.views_bb = nxt(), nxt()
-    w.sigma_w, w.sigma_b, w.rgb_w, w.rgb_b = nxt(), nxt(), nxt(), nxt()
-    beta = next(it)
-    w.sigmoid_beta = P(beta) if with_sdf else None
-    return w
-
-
-def render_args(B, H, W, N, cam, focal, near, far, styles, pix_x, pix_y, t_vals, t_rand,
-                sigma_noise, flags: dict, rgb, features, sdf, xyz, mask, ws, prepacked):
-    """sdfr_ngp_render_args (shared by the three networks' entry points)."""
-    P = _lib.ptr
-    a = _lib.NgpRenderArgs()
-    a.B, a.H, a.W, a.N = B, H, W, N
-    a.cam, a.focal, a.near_, a.far_ = P(cam), P(focal), P(near), P(far)
-    a.styles = P(styles)
-    a.pix_x, a.pix_y, a.t_vals = P(pix_x), P(pix_y), P(t_vals)
-    a.t_rand, a.sigma_noise = P(t_rand), P(sigma_noise)
-    a.t_rand_per_sample = int(flags["t_rand_per_sample"])
-    a.offset_sampling = int(flags["offset_sampling"])
-    a.static_viewdirs = int(flags["static_viewdirs"])
-    a.z_normalize = int(flags["z_normalize"])
-    a.force_background = int(flags["force_background"])
-    a.with_sdf = int(flags["with_sdf"])
-    a.rgb, a.features, a.sdf = P(rgb), P(features), P(sdf)
-    a.xyz, a.mask = P(xyz), P(mask)
-    a.workspace, a.workspace_bytes = P(ws), ws.numel()
-    a.field_precision = int(flags["field_precision"])
-    a.max_field_segments = int(flags["max_field_segments"])
-    a.prepacked = P(prepacked)
-    return a
-
-
-def workspace_bytes(kind: int, B: int, H: int, W: int, N: int, num_levels: int) -> int:
-    L = _lib.lib()
-    if kind == 2:
-        return L.sdfr_render_fc_workspace_bytes(B, H, W, N)
-    if kind == 1:
-        return L.sdfr_render_siren_workspace_bytes(B)
-    return L.sdfr_render_ngp_workspace_bytes(B, H, W, N, num_levels)
-
-
-FORWARD_FN = ("sdfr_render_ngp_forward", "sdfr_render_siren_forward", "sdfr_render_fc_forward")
-
-
 def _render_outputs(B, H, W, N, dev, output_features, return_sdf, return_xyz, empty,
                     absent_none=False):
     """(rgb, features, sdf, mask, xyz) of a render; an output that is not asked for is an
@@ -279,9 +200,7 @@ def render_fused(kind: int, params: List[Tensor], cam: Tensor, focal: Tensor, ne
     a = render_args(B, H, W, N, cam, focal, near, far, styles, pix_x, pix_y, t_vals, t_rand,
                     sigma_noise, f, rgb, _none_if_empty(features), _none_if_empty(sdf),
                     _none_if_empty(xyz), _none_if_empty(mask), ws, prepacked)
-    name = FORWARD_FN[kind]
-    _lib.check(getattr(_lib.lib(), name)(ctypes.byref(w), ctypes.byref(a), _lib.stream_of(cam)),
-               name)
+    render_forward(kind, w, a, _lib.stream_of(cam))
     return rgb, features, sdf, mask, xyz
 
 

@@ -18,7 +18,6 @@ structure on the GPU, with the hash-grid and SH encoders on the HIP kernels.
 """
 from __future__ import annotations
 
-import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -27,9 +26,9 @@ import torch.autograd as autograd
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, ops
 from .encoders import GridEncoder, SHEncoder
 from .linear import film_linear, linear
+from .render_calls import FusedCalls
 
 
 # ---------------------------------------------------------------------------
@@ -58,7 +57,6 @@ class LinearLayer(nn.Module):
     # the renderer networks' layers take the training kernels (linear.py); others F.linear
     train_kernels = False
     double_backward = False       # set by SirenGenerator (its eikonal loss, linear.py)
-    skip_identity = True          # False: the reference's literal 1 * y + 0 (A/B aid)
 
     def forward(self, input):
         # linear(): F.linear, or the split-fp16 MFMA kernels for the renderer MLP's
@@ -66,9 +64,9 @@ class LinearLayer(nn.Module):
         # the identity up to the sign of zero; skipping it saves two full passes over
         # the [rays, samples, 256] activation forward and one backward.
         y = linear(input, self.weight, self.bias, self.train_kernels, self.double_backward)
-        if self.std_init != 1 or not self.skip_identity:
+        if self.std_init != 1:
             y = self.std_init * y
-        if self.bias_init != 0 or not self.skip_identity:
+        if self.bias_init != 0:
             y = y + self.bias_init
         return y
 
@@ -111,6 +109,8 @@ class FiLMSiren(nn.Module):
 # ---------------------------------------------------------------------------
 class SirenGenerator(nn.Module):
     """FiLM-SIREN MLP, ``rendering.type == 'sdf'`` (sdf_model.py:101-139)."""
+
+    net_kind = 1                  # index into _lib.NETWORKS: the fused kernels' "siren"
 
     def __init__(self, D=8, W=256, style_dim=256, input_ch=3, input_ch_views=3, output_ch=4,
                  output_features=True):
@@ -163,6 +163,8 @@ def get_encoder(encoding, input_dim=3, multires=6, degree=4, num_levels=16, leve
 
 class NGPSIRENGenerator(nn.Module):
     """Hash-grid + FiLM-SIREN field, ``rendering.type == 'ngp'`` (sdf_model.py:1534-1596)."""
+
+    net_kind = 0                  # index into _lib.NETWORKS: the fused kernels' "ngp"
 
     def __init__(self, D=2, W=256, style_dim=256, output_features=True):
         super().__init__()
@@ -217,6 +219,8 @@ class FCGenerator(nn.Module):
     GEMMs (``linear.linear``; twice-differentiable: the eikonal term differentiates
     through them with create_graph); the per-face style_in (2 rows) stays on F.linear.
     CPU tensors take F.linear throughout."""
+
+    net_kind = 2                  # index into _lib.NETWORKS: the fused kernels' "fc"
 
     def __init__(self, D=8, W=256, style_dim=256, input_ch=3, input_ch_views=3, output_ch=4,
                  output_features=True):
@@ -273,21 +277,9 @@ def _opt(opt, key, default=None):
         return getattr(opt, key, default)
 
 
-def _per_face(x, B, device):
-    t = torch.as_tensor(x, dtype=torch.float32, device=device).reshape(-1)
-    return (t.expand(B) if t.numel() == 1 else t).contiguous()
-
-
 def _unit(x, dim):
     """``x / max(|x|, 1e-20)`` along ``dim`` (a zero vector stays zero)."""
     return x / x.norm(dim=dim, keepdim=True).clamp_min(1e-20)
-
-
-def _workspace(ws, need, device):
-    """``ws`` if it holds ``need`` bytes, else a new one that does."""
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-    return ws
 
 
 # What VolumeFeatureRenderer.render_geometry returns: NCHW maps and the per-sample SDF and
@@ -301,8 +293,10 @@ Surface = namedtuple("Surface", ("hit", "sample", "depth", "xyz", "normal", "rgb
                                  "sdf"))
 
 
-class VolumeFeatureRenderer(nn.Module):
-    """Drop-in for sdf_model.py:143-423 (same options, buffers, outputs)."""
+class VolumeFeatureRenderer(FusedCalls, nn.Module):
+    """Drop-in for sdf_model.py:143-423 (same options, buffers, outputs).  The fused HIP
+    path (``fused_forward`` and the library calls behind ``query``, ``query_gradient``,
+    ``render_geometry`` and ``render_surface``) is render_calls.FusedCalls."""
 
     def __init__(self, opt, style_dim=256, out_im_res=64, mode="train"):
         super().__init__()
@@ -523,251 +517,7 @@ class VolumeFeatureRenderer(nn.Module):
         target_values = pts.detach().norm(dim=-1) - ((far - near) / 4)
         return sdf, target_values
 
-    # ---------------------------------------------------------------- fused HIP path
-    def _net_kind(self):
-        """0 ngp, 1 siren, 2 fc (the library's net index), None: no fused kernel."""
-        net = self.network
-        if isinstance(net, NGPSIRENGenerator):
-            return 0
-        if isinstance(net, SirenGenerator):
-            return 1
-        if isinstance(net, FCGenerator):
-            return 2
-        return None
-
-    def _fused_inputs_ok(self, x, styles, no_grad_on=()):
-        """What every fused call needs (the network's kind is the caller's to check first):
-        ``use_fused``, ``x`` on the GPU, styles [B,256] for a 256-wide network, and under
-        grad mode nothing that requires grad among styles, ``no_grad_on``, parameters."""
-        if not self.use_fused or not x.is_cuda or styles is None:
-            return False
-        if styles.dim() != 2 or styles.shape[1] != 256 or self.network.W != 256:
-            return False
-        if torch.is_grad_enabled() and (styles.requires_grad or any(
-                t.requires_grad for t in (*no_grad_on, *self.parameters()))):
-            return False
-        return True
-
-    def _fused_ok(self, cam_poses, styles, return_eikonal):
-        kind = self._net_kind()
-        if kind is None or return_eikonal:
-            return False
-        if kind and (self.field_precision != "f16x3" or self.network.D != 8 or
-                     len(self.network.pts_linears) != (8 if kind == 1 else 7)):
-            return False
-        return self._fused_inputs_ok(cam_poses, styles)
-
-    def _weight_tensors(self, kind):
-        """The network's tensors in the order of ops.weights_struct / sdfr::render_fused
-        (ngp: table, offsets, input_linear; FC: x_in, style_in, pts, views; ngp / SIREN:
-        w, b, gamma w, b, beta w, b of every FiLM layer and views_linears; then the sigma
-        and rgb heads and sigmoid_beta -- a placeholder without an SDF)."""
-        net = self.network
-        if kind == 0:
-            ts = [net.encoder.embeddings, net.encoder.offsets, net.input_linear.weight,
-                  net.input_linear.bias]
-        elif kind == 2:
-            ts = [net.x_in.weight, net.x_in.bias, net.style_in.weight, net.style_in.bias]
-            for layer in net.pts_linears:
-                ts += [layer.weight, layer.bias]
-            ts += [net.views_linears.weight, net.views_linears.bias]
-        else:
-            ts = []
-        if kind != 2:
-            for layer in list(net.pts_linears) + [net.views_linears]:
-                ts += [layer.weight, layer.bias, layer.gamma.weight, layer.gamma.bias,
-                       layer.beta.weight, layer.beta.bias]
-        ts += [net.sigma_linear.weight, net.sigma_linear.bias, net.rgb_linear.weight,
-               net.rgb_linear.bias, self.sigmoid_beta if self.with_sdf else net.rgb_linear.bias]
-        return ts
-
-    def _weight_scalars(self, kind):
-        """(fscal, iscal) of ops.weights_struct."""
-        net = self.network
-        if kind == 0:
-            return ([float(np.log2(net.encoder.per_level_scale)), float(net.bound)],
-                    [int(net.encoder.base_resolution)])
-        return [], [int(net.D), int(net.W)]
-
-    def _weight_struct(self, kind):
-        fs, is_ = self._weight_scalars(kind)
-        return ops.weights_struct(kind, self._weight_tensors(kind), fs, is_, self.with_sdf)
-
-    def _fused_check_params(self):
-        net = self.network
-        if isinstance(net, FCGenerator):
-            if net.D != 8 or net.W != 256 or len(net.pts_linears) != 7:
-                raise RuntimeError("fused fc renderer supports the SDFace FCGenerator "
-                                   "(D=8, W=256) only")
-        elif isinstance(net, SirenGenerator):
-            if net.D != 8 or net.W != 256 or net.input_ch_views != 3:
-                raise RuntimeError("fused siren renderer supports the SDFace SirenGenerator "
-                                   "(D=8, W=256) only")
-        elif len(net.pts_linears) != 3 or net.encoder.num_levels != 16 or \
-                net.encoder.level_dim != 2 or net.encoder_dir.degree != 4:
-            raise RuntimeError("fused ngp renderer supports the SDFace NGPSIRENGenerator only")
-        for p in self.parameters():
-            if not p.is_contiguous() or p.dtype != torch.float32:
-                raise RuntimeError("fused ngp renderer needs contiguous fp32 parameters")
-
-    def _fused_inputs(self, cam_poses, focal, near, far, styles, t_rand):
-        """A camera call's inputs as the library takes them (contiguous fp32 on the cameras'
-        device): ``cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals``.
-        ``t_rand`` is None without ``perturb``, else [B,H,W] or (``per_sample`` = 1)
-        [B,H,W,N], drawn here when none was given."""
-        dev = cam_poses.device
-        B = cam_poses.shape[0]
-        cam = cam_poses.detach().float().contiguous()
-        focal = _per_face(focal, B, dev)
-        near = _per_face(near, B, dev)
-        far = _per_face(far, B, dev)
-        styles = styles.detach().float().contiguous()
-        per_sample = 0
-        if self.perturb > 0:
-            shape = (B, self.out_im_res, self.out_im_res)
-            if not self.offset_sampling:
-                shape += (self.N_samples,)
-                per_sample = 1
-            if t_rand is None:
-                t_rand = self._draw_t_rand(shape, dev)
-            t_rand = t_rand.to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
-        else:
-            t_rand = None
-        pix_x = self.i[0, 0, :].contiguous()
-        pix_y = self.j[0, :, 0].contiguous()
-        t_vals = self.t_vals.reshape(-1).contiguous()
-        return cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals
-
-    def fused_forward(self, cam_poses, focal, near, far, styles, t_rand=None, encode_only=False,
-                      styles_event=None, feat_mod=None):
-        """The whole ngp render on libsdfr (no autograd).  Returns the same tuple
-        as ``forward`` (rgb, features, sdf, mask, xyz, None).  ``styles_event``: a
-        torch.cuda.Event after which ``styles`` is ready (computed on another
-        stream): the library enqueues the sample geometry and the hash-grid gather
-        before its wait on it (ABI 11).  ``feat_mod`` [B,256] (ngp / FC f16x3): the
-        features come back as features * feat_mod in the decoder's split-NHWC fp16
-        layout [B,H,W,32,2,8] (ABI 12; sdfr_modulate_to_nhwc_split's output, bit for bit)
-        instead of NCHW fp32."""
-        self._fused_check_params()
-        dev = cam_poses.device
-        if styles_event is not None and not (styles.dtype == torch.float32
-                                             and styles.is_contiguous()):
-            # a conversion would read the styles on this stream: wait here instead
-            torch.cuda.current_stream(dev).wait_event(styles_event)
-            styles_event = None
-        B = cam_poses.shape[0]
-        H = W = self.out_im_res
-        N = self.N_samples
-        cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals = \
-            self._fused_inputs(cam_poses, focal, near, far, styles, t_rand)
-        noise = None
-        if not self.with_sdf and self.raw_noise_std > 0:
-            noise = torch.randn(B, H, W, N, device=dev) * self.raw_noise_std
-        kind = self._net_kind()
-        if feat_mod is not None and (kind == 1 or self.field_precision != "f16x3"
-                                     or not self.output_features):
-            feat_mod = None                      # SIREN / fp32 field: NCHW features
-        if self.field_precision not in ("f16x3", "fp32"):
-            raise ValueError(f"field_precision must be 'f16x3' or 'fp32', "
-                             f"got {self.field_precision!r}")
-        if kind and encode_only:
-            raise RuntimeError("only the ngp renderer has a hash-grid encode stage")
-        flags = dict(
-            t_rand_per_sample=per_sample, offset_sampling=int(self.offset_sampling),
-            static_viewdirs=int(bool(self.static_viewdirs)), z_normalize=int(self.z_normalize),
-            force_background=int(bool(self.force_background)), with_sdf=int(self.with_sdf),
-            field_precision=(_lib.FIELD_FP32 if self.field_precision == "fp32"
-                             else _lib.FIELD_F16X3),
-            max_field_segments=int(self.max_field_segments),
-            output_features=int(bool(self.output_features)),
-            return_sdf=int(bool(self.return_sdf)), return_xyz=int(bool(self.return_xyz)))
-        prepacked = self._prepacked(kind, cam) if self.field_precision == "f16x3" else None
-        if (styles_event is None and feat_mod is None and not encode_only
-                and self.stage_events is None and self.field_event is None):
-            # the plain call: the registered op (ops.py), outputs allocated there
-            fs, is_ = self._weight_scalars(kind)
-            out = torch.ops.sdfr.render_fused(
-                kind, self._weight_tensors(kind), cam, focal, near, far, styles, t_rand, noise,
-                pix_x, pix_y, t_vals, prepacked, fs, is_, [flags[k] for k in ops.RENDER_FLAGS],
-                H, W, N)
-            rgb, features, sdf, mask, xyz = map(ops._none_if_empty, out)
-            return rgb, features, sdf, mask, xyz, None
-        # with events (stage timing, the styles hand-off of Generator.forward), the
-        # decoder-layout feature store or the encode stage alone: the library directly
-        rgb, features, sdf, mask, xyz = ops._render_outputs(
-            B, H, W, N, dev, self.output_features and feat_mod is None, self.return_sdf,
-            self.return_xyz, torch.empty, absent_none=True)
-        feat_split = (torch.empty(B, H, W, 32, 2, 8, device=dev, dtype=torch.float16)
-                      if feat_mod is not None else None)
-        num_levels = self.network.encoder.num_levels if kind == 0 else 0
-        ws = torch.empty(ops.workspace_bytes(kind, B, H, W, N, num_levels), dtype=torch.uint8,
-                         device=dev)
-        a = ops.render_args(B, H, W, N, cam, focal, near, far, styles, pix_x, pix_y, t_vals,
-                            t_rand, noise, flags, rgb, features, sdf, xyz, mask, ws, prepacked)
-        if self.stage_events is not None:
-            for k, ev in enumerate(self.stage_events):
-                if ev is not None:               # (None: that point is not timed)
-                    a.stage_events[k] = ctypes.c_void_p(ev.cuda_event)
-        if self.field_event is not None:
-            a.field_event = ctypes.c_void_p(self.field_event.cuda_event)
-        if styles_event is not None:
-            a.styles_event = ctypes.c_void_p(styles_event.cuda_event)
-        if feat_split is not None:
-            feat_mod = feat_mod.detach().float().contiguous()
-            a.features_split, a.features_mod = _lib.ptr(feat_split), _lib.ptr(feat_mod)
-            features = feat_split
-        w = self._weight_struct(kind)
-        if encode_only:
-            _lib.check(_lib.lib().sdfr_render_ngp_encode_only(
-                ctypes.byref(w), ctypes.byref(a), _lib.stream_of(cam)), "sdfr_render_ngp_encode_only")
-            return ws
-        name = ops.FORWARD_FN[kind]
-        _lib.check(getattr(_lib.lib(), name)(ctypes.byref(w), ctypes.byref(a), _lib.stream_of(cam)),
-                   name)
-        return rgb, features, sdf, mask, xyz, None
-
-    def _prepacked(self, kind, like, grad=False):
-        """The field kernel's split-fp16 weight packing (row scales, scaled biases,
-        MFMA fragments: sdfr_render_*_pack), redone only when a network parameter
-        changed (data pointer or in-place version), not per call.  ``grad``: the SIREN
-        gradient kernel's own packing of the SDF trunk (sdfr_query_siren_grad_pack), kept
-        in a cache entry of its own beside the render's."""
-        key = (kind,) + tuple((p.data_ptr(), p._version) for p in self.network.parameters())
-        attr = "_grad_pack_cache" if grad else "_pack_cache"
-        cache = getattr(self, attr, None)
-        if cache is not None and cache[0] == key:
-            return cache[1]
-        L = _lib.lib()
-        if grad:
-            nbytes, name = L.sdfr_query_siren_grad_pack_bytes(), "sdfr_query_siren_grad_pack"
-        else:
-            nbytes = L.sdfr_render_pack_bytes(int(kind))
-            name = ("sdfr_render_ngp_pack", "sdfr_render_siren_pack", "sdfr_render_fc_pack")[kind]
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=like.device)
-        w = self._weight_struct(kind)
-        _lib.check(getattr(L, name)(ctypes.byref(w), _lib.ptr(buf), _lib.stream_of(like)), name)
-        setattr(self, attr, (key, buf))
-        return buf
-
     # ---------------------------------------------------------------- point query
-    # Points per library call of the fused query.  The ngp workspace is about 144 bytes per
-    # point (the 32 gathered features, the grid coordinate) plus 0.9 MB, so 2^20 points
-    # bound it at ~152 MB; at 32 points per group that is 512 workgroups, two per CU.  (The
-    # SIREN calls' workspace does not grow with the points; they share the chunking.)
-    QUERY_CHUNK_POINTS = 1 << 20
-
-    def _query_fused_ok(self, points, styles):
-        """The rule of ``_fused_ok`` for a point query (the fused query and gradient exist
-        for the three networks on the f16x3 field kernel; SIREN and FC in the shape their
-        kernels are built for: D = 8, W = 256)."""
-        kind = self._net_kind()
-        if kind is None or self.field_precision != "f16x3":
-            return False
-        if kind and (self.network.D != 8 or
-                     len(self.network.pts_linears) != (8 if kind == 1 else 7)):
-            return False
-        return self._fused_inputs_ok(points, styles, no_grad_on=(points,))
-
     def query(self, points, styles, viewdirs=None, return_rgb=True, chunk_groups=None):
         """The field itself at arbitrary points: ``(sdf [B,M], rgb [B,M,3] | None)``.
 
@@ -824,72 +574,7 @@ class VolumeFeatureRenderer(nn.Module):
         sdf = sdf.reshape(B, R * N)[:, :M]
         return sdf, (rgb.reshape(B, R * N, 3)[:, :M] if return_rgb else None)
 
-    def _fused_query(self, points, dirs, styles, return_rgb=True, chunk_groups=None):
-        """``sdfr_query_{ngp,siren,fc}_forward`` on grouped points:
-        ``points`` [B,R,N,3], ``dirs`` [B,R,3] (one per group) -> (sdf [B,R,N],
-        rgb [B,R,N,3] | None), in calls of at most ``chunk_groups`` groups per face."""
-        self._fused_check_params()
-        dev = points.device
-        B, R, N = points.shape[:3]
-        pts = points.detach().float().contiguous()
-        styles = styles.detach().float().contiguous()
-        sdf = torch.empty(B, R, N, device=dev)
-        rgb = torch.empty(B, R, N, 3, device=dev) if return_rgb else None
-        if chunk_groups is None:
-            chunk_groups = max(16, self.QUERY_CHUNK_POINTS // (B * N) // 16 * 16)
-        L = _lib.lib()
-        kind = self._net_kind()
-        prepacked = self._prepacked(kind, pts)
-        w = self._weight_struct(kind)
-        Args = (_lib.NgpQueryArgs, _lib.SirenQueryArgs, _lib.FcQueryArgs)[kind]
-        name = ("sdfr_query_ngp_forward", "sdfr_query_siren_forward",
-                "sdfr_query_fc_forward")[kind]
-        ws_bytes = (L.sdfr_query_ngp_workspace_bytes, L.sdfr_query_siren_workspace_bytes,
-                    L.sdfr_query_fc_workspace_bytes)[kind]
-        fn = getattr(L, name)
-
-        def call(r, ins, outs, ws):
-            a = Args(
-                B=B, R=r, N=N, points=_lib.ptr(ins[0]), dirs=_lib.ptr(ins[1]),
-                styles=_lib.ptr(styles), sdf=_lib.ptr(outs[0]), rgb=_lib.ptr(outs[1]),
-                workspace=_lib.ptr(ws), workspace_bytes=ws.numel(),
-                prepacked=_lib.ptr(prepacked))
-            _lib.check(fn(ctypes.byref(w), ctypes.byref(a), _lib.stream_of(pts)), name)
-
-        self._chunked_calls(R, chunk_groups, (pts, dirs.float()), (sdf, rgb),
-                            lambda r: ws_bytes(B, r, N), call)
-        return sdf, rgb
-
-    @staticmethod
-    def _chunked_calls(total, chunk, ins, outs, workspace_bytes, call):
-        """``call(n, ins, outs, ws)`` on at most ``chunk`` of the ``total`` entries along
-        dim 1 of the [B,total,..] tensors ``ins`` and ``outs`` (an output may be None) at a
-        time.  A chunk is a call of its own on contiguous tensors: the caller's own when
-        one chunk is the whole, else copies in and out.  The workspace grows to
-        ``workspace_bytes(n)``; the last one is returned."""
-        whole = total <= chunk
-        ws = None
-        for i0 in range(0, total, chunk):
-            i1 = min(total, i0 + chunk)
-            c_ins = [(t if whole else t[:, i0:i1]).contiguous() for t in ins]
-            c_outs = [t if whole or t is None else
-                      torch.empty((t.shape[0], i1 - i0) + t.shape[2:], device=t.device)
-                      for t in outs]
-            ws = _workspace(ws, workspace_bytes(i1 - i0), ins[0].device)
-            call(i1 - i0, c_ins, c_outs, ws)
-            if not whole:
-                for t, c in zip(outs, c_outs):
-                    if t is not None:
-                        t[:, i0:i1] = c
-        return ws
-
     # ---------------------------------------------------------------- SDF gradient
-    # Points per library call of the fused gradient.  The workspace is 512 bytes per
-    # point (the 32 gathered features and their 3 x 32 input derivatives) plus 0.9 MB, so
-    # 2^18 points bound it at ~135 MB; at 32 points per workgroup pass that is 8192
-    # passes over the call's 1024 workgroups.
-    GRADIENT_CHUNK_POINTS = 1 << 18
-
     def query_gradient(self, points, styles, normalize=False, chunk_points=None,
                        encode_only=False):
         """The SDF and its gradient at arbitrary points: ``(sdf [B,M], grad [B,M,3])``.
@@ -948,50 +633,6 @@ class VolumeFeatureRenderer(nn.Module):
             sdf = sdf.detach()
         return sdf, (_unit(grad, -1) if normalize else grad)
 
-    def _fused_gradient(self, points, styles, chunk_points=None, encode_only=False):
-        """``sdfr_query_{ngp,siren,fc}_grad`` on ``points`` [B,M,3] in
-        calls of at most ``chunk_points`` points per face."""
-        self._fused_check_params()
-        dev = points.device
-        B, M = points.shape[:2]
-        pts = points.detach().float().contiguous()
-        styles = styles.detach().float().contiguous()
-        sdf = torch.empty(B, M, device=dev)
-        grad = torch.empty(B, M, 3, device=dev)
-        if chunk_points is None:
-            chunk_points = self.GRADIENT_CHUNK_POINTS // B
-        chunk_points = max(32, int(chunk_points) // 32 * 32)
-        if encode_only:
-            chunk_points = max(chunk_points, M)      # one call: its workspace is the result
-        L = _lib.lib()
-        kind = self._net_kind()
-        # (SIREN: the gradient kernel's own packing of the trunk, cached beside the render's;
-        # ngp and FC: the render's packing)
-        prepacked = self._prepacked(kind, pts, grad=kind == 1)
-        w = self._weight_struct(kind)
-        Args = (_lib.NgpGradArgs, _lib.SirenGradArgs, _lib.FcGradArgs)[kind]
-        name = ("sdfr_query_ngp_grad", "sdfr_query_siren_grad", "sdfr_query_fc_grad")[kind]
-        ws_bytes = (L.sdfr_query_ngp_grad_workspace_bytes,
-                    L.sdfr_query_siren_grad_workspace_bytes,
-                    L.sdfr_query_fc_grad_workspace_bytes)[kind]
-        fn = getattr(L, name)
-
-        def call(m, ins, outs, ws):
-            a = Args(
-                B=B, M=m, points=_lib.ptr(ins[0]), styles=_lib.ptr(styles),
-                sdf=_lib.ptr(outs[0]), grad=_lib.ptr(outs[1]), workspace=_lib.ptr(ws),
-                workspace_bytes=ws.numel(), prepacked=_lib.ptr(prepacked))
-            _lib.check(fn(ctypes.byref(w), ctypes.byref(a), _lib.stream_of(pts)), name)
-
-        ws = self._chunked_calls(M, chunk_points, (pts,), (sdf, grad),
-                                 lambda m: ws_bytes(B, m), call)
-        if encode_only:
-            # the workspace starts with the gather's output [B][Mp][4][32], Mp = M up to 8
-            Mp = (M + 7) // 8 * 8
-            gd = ws[:B * Mp * 512].view(torch.float32).view(B, Mp, 4, 32)[:, :M]
-            return gd[:, :, 0].clone(), gd[:, :, 1:].clone()
-        return sdf, grad
-
     # ---------------------------------------------------------------- geometry render
     GEOMETRY_FIELDS = ("normal", "depth", "xyz", "mask", "sdf", "eikonal")
 
@@ -1039,72 +680,6 @@ class VolumeFeatureRenderer(nn.Module):
             out["normal"] = _unit(out["normal"], 1)
         return Geometry(**{k: out.get(k) for k in self.GEOMETRY_FIELDS})
 
-    def _fused_geometry(self, cam_poses, focal, near, far, styles, t_rand, want, chunk_points):
-        """``sdfr_render_ngp_geometry`` in calls of whole faces or bands of whole rows."""
-        self._fused_check_params()
-        dev = cam_poses.device
-        B = cam_poses.shape[0]
-        H = W = self.out_im_res
-        N = self.N_samples
-        cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals = \
-            self._fused_inputs(cam_poses, focal, near, far, styles, t_rand)
-        shapes = {"sdf": (B, H, W, N), "eikonal": (B, H, W, N, 3), "normal": (B, 3, H, W),
-                  "depth": (B, 1, H, W), "xyz": (B, 3, H, W), "mask": (B, 1, H, W)}
-        out = {k: torch.empty(shapes[k], device=dev) for k in want}
-        if chunk_points is None:
-            chunk_points = self.GRADIENT_CHUNK_POINTS
-        chunk_points = max(1, int(chunk_points))
-        per_row, per_face = W * N, H * W * N
-        if per_face <= chunk_points:
-            # whole faces; the library takes fewer than 2^25 padded points per call
-            padded = (per_face + 7) // 8 * 8
-            faces, rows = max(1, min(chunk_points // per_face, ((1 << 25) - 1) // padded)), H
-        else:
-            faces, rows = 1, max(1, chunk_points // per_row)
-        L = _lib.lib()
-        prepacked = self._prepacked(0, cam)
-        w = self._weight_struct(0)
-        ws = None
-        for b0 in range(0, B, faces):
-            b1 = min(B, b0 + faces)
-            for y0 in range(0, H, rows):
-                y1 = min(H, y0 + rows)
-                # per-sample outputs of a band are contiguous in the result; a band of a
-                # map is not: it goes through a tensor of its own
-                dst, tmp = {}, {}
-                for k, t in out.items():
-                    v = t[b0:b1, y0:y1] if k in ("sdf", "eikonal") else t[b0:b1, :, y0:y1]
-                    dst[k] = v if v.is_contiguous() else torch.empty(v.shape, device=dev)
-                    if dst[k] is not v:
-                        tmp[k] = v
-                c_rand = None
-                if t_rand is not None:
-                    c_rand = t_rand[b0:b1, y0:y1].contiguous()
-                ws = _workspace(ws, L.sdfr_render_ngp_geometry_workspace_bytes(
-                    b1 - b0, y1 - y0, W, N), dev)
-                c_y = pix_y[y0:y1]
-                a = _lib.NgpGeometryArgs(
-                    B=b1 - b0, H=y1 - y0, W=W, N=N, cam=_lib.ptr(cam[b0:b1]),
-                    focal=_lib.ptr(focal[b0:b1]), near_=_lib.ptr(near[b0:b1]),
-                    far_=_lib.ptr(far[b0:b1]), styles=_lib.ptr(styles[b0:b1]),
-                    pix_x=_lib.ptr(pix_x), pix_y=_lib.ptr(c_y), t_vals=_lib.ptr(t_vals),
-                    t_rand=_lib.ptr(c_rand), t_rand_per_sample=per_sample,
-                    offset_sampling=int(self.offset_sampling), z_normalize=int(self.z_normalize),
-                    force_background=int(bool(self.force_background)),
-                    sdf=_lib.ptr(dst.get("sdf")), eikonal=_lib.ptr(dst.get("eikonal")),
-                    normal=_lib.ptr(dst.get("normal")), depth=_lib.ptr(dst.get("depth")),
-                    xyz=_lib.ptr(dst.get("xyz")), mask=_lib.ptr(dst.get("mask")),
-                    workspace=_lib.ptr(ws), workspace_bytes=ws.numel(),
-                    prepacked=_lib.ptr(prepacked))
-                _lib.check(L.sdfr_render_ngp_geometry(ctypes.byref(w), ctypes.byref(a),
-                                                      _lib.stream_of(cam)),
-                           "sdfr_render_ngp_geometry")
-                for k, v in tmp.items():
-                    v.copy_(dst[k])
-        if "sdf" in out:
-            out["sdf"] = out["sdf"].unsqueeze(-1)
-        return out
-
     def _module_geometry(self, cam_poses, focal, near, far, styles, t_rand, want):
         """``render_geometry`` op by op: the rays, samples and weights of ``render``, the
         gradient by autograd on detached inputs."""
@@ -1140,12 +715,6 @@ class VolumeFeatureRenderer(nn.Module):
 
     # ---------------------------------------------------------------- surface render
     SURFACE_FIELDS = Surface._fields
-    # Samples per library call of the fused surface render.  A bisection step evaluates only
-    # H W points per face, a few workgroups' worth, so a call should hold as many faces as
-    # it can: 2^22 samples take 32 faces of 64^2 x 24 or one of 128^2 x 128 in one call (four
-    # calls of 2^20 samples took twice as long).  The ngp workspace is about 170 bytes per
-    # sample, ~0.7 GB at this bound; the SIREN's about 25.
-    SURFACE_CHUNK_POINTS = 1 << 22
 
     def render_surface(self, cam_poses, focal, near, far, styles, t_rand=None, refine_steps=8,
                        want=("hit", "depth", "xyz", "normal", "rgb"), chunk_points=None):
@@ -1195,82 +764,6 @@ class VolumeFeatureRenderer(nn.Module):
         path = self._fused_surface if fused else self._module_surface
         out = path(cam_poses, focal, near, far, styles, t_rand, refine_steps, want, chunk_points)
         return Surface(**{k: out.get(k) for k in self.SURFACE_FIELDS})
-
-    def _fused_surface(self, cam_poses, focal, near, far, styles, t_rand, refine_steps, want,
-                       chunk_points):
-        """``sdfr_render_{ngp,siren}_surface`` in calls of whole faces or bands of rows."""
-        self._fused_check_params()
-        dev = cam_poses.device
-        B = cam_poses.shape[0]
-        H = W = self.out_im_res
-        N = self.N_samples
-        cam, focal, near, far, styles, t_rand, per_sample, pix_x, pix_y, t_vals = \
-            self._fused_inputs(cam_poses, focal, near, far, styles, t_rand)
-        shapes = {k: (B, 3 if k in ("xyz", "normal", "rgb") else 1, H, W)
-                  for k in self.SURFACE_FIELDS}
-        shapes["sdf"] = (B, H, W, N)
-        out = {k: torch.empty(shapes[k], device=dev,
-                              dtype=torch.int32 if k == "sample" else torch.float32)
-               for k in want}
-        if chunk_points is None:
-            chunk_points = self.SURFACE_CHUNK_POINTS
-        chunk_points = max(1, int(chunk_points))
-        per_row, per_face = W * N, H * W * N
-        if per_face <= chunk_points:
-            faces, rows = max(1, chunk_points // per_face), H
-        else:
-            faces, rows = 1, max(1, chunk_points // per_row)
-        L = _lib.lib()
-        kind = self._net_kind()
-        net = ("ngp", "siren")[kind]
-        fn = getattr(L, f"sdfr_render_{net}_surface")
-        ws_bytes = getattr(L, f"sdfr_render_{net}_surface_workspace_bytes")
-        prepacked = self._prepacked(kind, cam)
-        needs_grad = kind == 1 and ("normal" in want or "residual" in want)
-        prepacked_grad = self._prepacked(kind, cam, grad=True) if needs_grad else None
-        w = self._weight_struct(kind)
-        ws = None
-        for b0 in range(0, B, faces):
-            b1 = min(B, b0 + faces)
-            for y0 in range(0, H, rows):
-                y1 = min(H, y0 + rows)
-                # the coarse SDF of a band is contiguous in the result; a band of a map is
-                # not: it goes through a tensor of its own
-                dst, tmp = {}, {}
-                for k, t in out.items():
-                    v = t[b0:b1, y0:y1] if k == "sdf" else t[b0:b1, :, y0:y1]
-                    dst[k] = v if v.is_contiguous() else torch.empty(v.shape, device=dev,
-                                                                     dtype=v.dtype)
-                    if dst[k] is not v:
-                        tmp[k] = v
-                c_rand = None
-                if t_rand is not None:
-                    c_rand = t_rand[b0:b1, y0:y1].contiguous()
-                need = ws_bytes(b1 - b0, y1 - y0, W, N)
-                if need == 0:
-                    raise ValueError("render_surface: too many points in one call; lower "
-                                     "chunk_points")
-                ws = _workspace(ws, need, dev)
-                c_y = pix_y[y0:y1]
-                a = _lib.SurfaceArgs(
-                    B=b1 - b0, H=y1 - y0, W=W, N=N, cam=_lib.ptr(cam[b0:b1]),
-                    focal=_lib.ptr(focal[b0:b1]), near_=_lib.ptr(near[b0:b1]),
-                    far_=_lib.ptr(far[b0:b1]), styles=_lib.ptr(styles[b0:b1]),
-                    pix_x=_lib.ptr(pix_x), pix_y=_lib.ptr(c_y), t_vals=_lib.ptr(t_vals),
-                    t_rand=_lib.ptr(c_rand), t_rand_per_sample=per_sample,
-                    offset_sampling=int(self.offset_sampling),
-                    static_viewdirs=int(bool(self.static_viewdirs)),
-                    z_normalize=int(self.z_normalize), refine_steps=refine_steps,
-                    workspace=_lib.ptr(ws), workspace_bytes=ws.numel(),
-                    prepacked=_lib.ptr(prepacked), prepacked_grad=_lib.ptr(prepacked_grad),
-                    **{k: _lib.ptr(dst.get(k)) for k in self.SURFACE_FIELDS})
-                _lib.check(fn(ctypes.byref(w), ctypes.byref(a), _lib.stream_of(cam)),
-                           f"sdfr_render_{net}_surface")
-                for k, v in tmp.items():
-                    v.copy_(dst[k])
-        if "sdf" in out:
-            out["sdf"] = out["sdf"].unsqueeze(-1)
-        return out
 
     def _module_surface(self, cam_poses, focal, near, far, styles, t_rand, refine_steps, want,
                         chunk_points=None):

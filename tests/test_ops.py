@@ -1,6 +1,7 @@
 """torch.library registration of the hot-path ops (sdface-gan_amd/ops.py):
 schemas, FakeTensor shape propagation and the reference's device errors, on the CPU.
 The ops' results are checked on the GPU (tests/test_gpu_ops.py)."""
+import ctypes
 import pytest
 import torch
 from torch._subclasses.fake_tensor import FakeTensorMode
@@ -79,6 +80,36 @@ def test_weight_tensors_order(sdfr):
     assert len(ren._weight_tensors(0)) == 4 + 6 * 3 + 6 + 4 + 1
     assert ren._weight_tensors(0)[0] is ren.network.encoder.embeddings
     assert ren._weight_tensors(0)[-1] is ren.sigmoid_beta
+
+
+@pytest.mark.parametrize("kind, net", [(0, dict()), (1, dict(ngp=False)),
+                                       (2, dict(ngp=False, fc=True))])
+def test_weight_tensors_follow_the_network_table(sdfr, kind, net):
+    """The flat list is one tensor per name of _lib.NETWORKS[kind].fields, in that order,
+    and weights_struct puts each into the struct member of that name."""
+    ren = sdfr.VolumeFeatureRenderer(sdfr.vol_render_opt(**net).rendering, style_dim=256,
+                                     out_im_res=8)
+    assert ren._net_kind() == kind
+    row = sdfr._lib.NETWORKS[kind]
+    ts = ren._weight_tensors(kind)
+    assert len(ts) == len(row.fields) == len(set(row.fields))
+    assert len({t.data_ptr() for t in ts}) == len(ts)
+    w = ren._weight_struct(kind)
+    assert type(w) is row.weights
+    for name, t in zip(row.fields, ts):
+        member, _, index = name.partition("[")
+        got = getattr(w, member)[int(index[:-1])] if index else getattr(w, member)
+        assert got == t.data_ptr(), name
+    named = dict(ren.named_parameters())
+    assert ts[row.fields.index("sigma_w")] is named["network.sigma_linear.weight"]
+    assert ts[row.fields.index("pts_b[2]")] is named["network.pts_linears.2.bias"]
+    assert ts[row.fields.index("views_w")] is named["network.views_linears.weight"]
+    assert ts[-1] is ren.sigmoid_beta and row.fields[-1] == "sigmoid_beta"
+    # every tensor member of the struct is in the table
+    pointers = {n if not hasattr(t, "_length_") else f"{n}[{i}]"
+                for n, t in row.weights._fields_ for i in range(getattr(t, "_length_", 1))
+                if t is ctypes.c_void_p or getattr(t, "_type_", None) is ctypes.c_void_p}
+    assert pointers == set(row.fields)
 
 
 def test_ops_raise_on_host_tensors(ops):
