@@ -1066,6 +1066,69 @@ int sdfr_mc_sparse_emit(const float *values, const int32_t *slots, const uint8_t
                         size_t ws_bytes, float *verts, int32_t *faces, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Mesh connected components (added to ABI 15 without a version step: additive;
+ * csrc/mesh_cc.hip): label, measure, keep, compact -- where users of the reference call
+ * trimesh's mesh.split() on the host and keep the big piece.
+ *
+ * Mesh: faces [F,3] int32 (F may be 0) over V vertices, verts [V,3] fp32, device.
+ * 1 <= V < 2^31 and 3 F < 2^31.  Two vertices are connected when a face references both;
+ * a vertex no face references is a component of its own with 0 faces.
+ *
+ *   sdfr_mesh_cc_label:  lock-free union-find over the face edges (every hook puts the
+ *                       larger root under the smaller), then a flatten pass: label[v] =
+ *                       the SMALLEST vertex index of v's component -- a pure function of
+ *                       the mesh, whatever the scheduling.  comp[v] = the dense id of that
+ *                       component: ids 0..C-1 in increasing order of the smallest vertex.
+ *                       C goes to HOST memory *n_components (synchronises stream).
+ *   sdfr_mesh_cc_stats:  per component (C = the label call's count, comp its output):
+ *                       n_vertices, n_faces [C] uint32; bbox [C,6] fp32 = min x y z, max
+ *                       x y z over the component's vertices; area_q [C] uint64, the sum of
+ *                       the faces' areas in units of *area_unit (HOST; synchronises).
+ *                       Integer atomics only: every output is reproducible bit for bit.
+ *                       Unit: with d the largest edge of the mesh's bounding box and
+ *                       x = 2 d^2 max(F, 1), u = 2^(k - 61), k = the exponent frexp(x)
+ *                       gives (x <= 2^k < 2 x); u = 1 when x is 0 or not finite.  A face's
+ *                       area, 0.5 |(b - a) x (c - a)| in fp64 from the fp32 vertices, is
+ *                       divided by u and rounded to nearest; no sum can reach 2^62.
+ *                       |area_q[c] u - exact| <= n_faces[c] u / 2 + 2^11 u (the second
+ *                       term covers the fp64 evaluation over the whole mesh).
+ *   sdfr_mesh_cc_select_count: keep [C] uint8 (device).  A face is kept when
+ *                       keep[comp[its first vertex]]; a vertex when keep[comp[v]] and,
+ *                       with drop_unreferenced != 0, a kept face references it.  Flags
+ *                       and their scans go into ws; counts[0] = kept vertices, counts[1] =
+ *                       kept faces to HOST memory (synchronises stream).
+ *   sdfr_mesh_cc_select_emit: same mesh and ws (after the count), V_out / F_out the counts:
+ *                       verts_out [V_out,3], faces_out [F_out,3] int32 reindexed,
+ *                       index_map [V_out] int32 (new -> old vertex).  Kept vertices and
+ *                       kept faces keep their original relative order.
+ *
+ * ws: sdfr_mesh_cc_workspace_bytes(V, F) bytes for every call (4 bytes per vertex and
+ * per face + the scans' block sums + 1 KB; 0 for sizes outside the limits above).
+ * SDFR_EINVAL before any launch, nothing written, for null pointers (faces may be null
+ * when F is 0), V == 0, V or 3 F >= 2^31, a short workspace, C outside [1, V], V_out
+ * outside [1, V] or F_out > F.  A face index outside [0, V) (or a comp entry outside
+ * [0, C)) is never dereferenced: the kernels skip the element and set a device error word,
+ * which the three synchronising calls read with their counts and return as SDFR_EINVAL
+ * (device outputs are then unspecified, *n_components / counts / *area_unit unwritten).
+ * Everything but those host reads is asynchronous on stream; nothing allocates.
+ * ------------------------------------------------------------------------- */
+size_t sdfr_mesh_cc_workspace_bytes(uint32_t V, uint32_t F);
+int sdfr_mesh_cc_label(const int32_t *faces, uint32_t V, uint32_t F, int32_t *label,
+                       int32_t *comp, void *ws, size_t ws_bytes, uint32_t *n_components,
+                       void *stream);
+int sdfr_mesh_cc_stats(const float *verts, const int32_t *faces, const int32_t *comp,
+                       uint32_t V, uint32_t F, uint32_t C, uint32_t *n_vertices,
+                       uint32_t *n_faces, float *bbox, uint64_t *area_q, double *area_unit,
+                       void *ws, size_t ws_bytes, void *stream);
+int sdfr_mesh_cc_select_count(const int32_t *faces, const int32_t *comp, const uint8_t *keep,
+                              uint32_t V, uint32_t F, uint32_t C, int drop_unreferenced,
+                              void *ws, size_t ws_bytes, uint32_t *counts, void *stream);
+int sdfr_mesh_cc_select_emit(const float *verts, const int32_t *faces, uint32_t V, uint32_t F,
+                             uint32_t V_out, uint32_t F_out, const void *ws, size_t ws_bytes,
+                             float *verts_out, int32_t *faces_out, int32_t *index_map,
+                             void *stream);
+
+/* ---------------------------------------------------------------------------
  * Mesh rasteriser (added to ABI 15 without a version step: additive; csrc/raster.hip):
  * B views of one indexed mesh with the render's own pinhole camera, the nearest triangle
  * per pixel, deterministic.  Where the reference rasterises with pytorch3d

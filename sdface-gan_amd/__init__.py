@@ -24,7 +24,11 @@ bisection, with the unit normal and the field's colour there, fused:
 sdfr_render_ngp_surface / sdfr_render_siren_surface), shade_surface (a lit view of it);
 extract_mesh_sparse / Generator.extract_mesh (the field's mesh at up to 1024^3 from
 narrow-band 8^3 bricks, grown along the surface: csrc/mesh_sparse.hip), sparse_extract (the
-generic driver), SparseVolume, cube_axis; rasterize_mesh -> Raster (B views of a Mesh, nearest
+generic driver), SparseVolume, cube_axis; mesh_components -> Components / keep_components
+(a mesh's connected components labelled, measured, filtered and compacted on the GPU:
+csrc/mesh_cc.hip, sdfr_mesh_cc_*; label_components, component_stats, sparse_mesh the pieces;
+extract_mesh_sparse(components={"largest": 1}) filters before the host copy);
+rasterize_mesh -> Raster (B views of a Mesh, nearest
 triangle per pixel with depth and perspective-correct barycentrics, deterministic:
 csrc/raster.hip, sdfr_mesh_raster), interpolate_vertex_attributes (sdfr_mesh_interpolate),
 render_mesh (the Surface of a mesh), load_obj, subdivide_mesh; with them
@@ -41,10 +45,11 @@ from .generator import (Blur, Decoder, EqualLinear, FusedLeakyReLU, Generator,  
                         MappingLinear, ModulatedConv2d, NoiseInjection, PixelNorm, StyledConv,
                         ToRGB, Upsample, fused_leaky_relu, make_kernel, upfirdn2d)
 from .graphs import GraphedGenerator  # noqa: F401
-from .mesh import (Mesh, SparseVolume, align_volume, color_mesh, cube_axis,  # noqa: F401
-                   cube_points, eikonal_residual, extract_mesh_sparse,
-                   extract_mesh_with_marching_cubes, marching_cubes, normal_mesh, sdf_cube,
-                   shade_surface, sparse_extract, world_to_network, xyz2mesh)
+from .mesh import (Components, Mesh, SparseVolume, align_volume, color_mesh,  # noqa: F401
+                   component_stats, cube_axis, cube_points, eikonal_residual,
+                   extract_mesh_sparse, extract_mesh_with_marching_cubes, keep_components,
+                   label_components, marching_cubes, mesh_components, normal_mesh, sdf_cube,
+                   shade_surface, sparse_extract, sparse_mesh, world_to_network, xyz2mesh)
 from .raster import (Raster, interpolate_vertex_attributes, load_obj, rasterize_mesh,  # noqa: F401
                      render_mesh, subdivide_mesh)
 from .options import AttrDict, SDFOptions, vol_render_opt  # noqa: F401

@@ -317,6 +317,14 @@ PROTOTYPES = {
     "sdfr_mc_sparse_workspace_bytes": (_sz, [_u32]),
     "sdfr_mc_sparse_count": (_int, _MC_SPARSE + [_P(_u32), _vp]),
     "sdfr_mc_sparse_emit": (_int, _MC_SPARSE + [_vp, _vp]),
+    "sdfr_mesh_cc_workspace_bytes": (_sz, [_u32] * 2),
+    "sdfr_mesh_cc_label": (_int, [_vp, _u32, _u32, _vp, _vp, _vp, _sz, _P(_u32), _vp]),
+    "sdfr_mesh_cc_stats": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp,
+                                  _P(ctypes.c_double), _vp, _sz, _vp]),
+    "sdfr_mesh_cc_select_count": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _int, _vp, _sz,
+                                         _P(_u32), _vp]),
+    "sdfr_mesh_cc_select_emit": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _vp,
+                                        _vp, _vp]),
     "sdfr_mesh_raster_workspace_bytes": (_sz, [_u32] * 5),
     "sdfr_mesh_raster": (_int, [_P(RasterArgs), _vp]),
     "sdfr_mesh_interpolate": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32,

@@ -1060,7 +1060,8 @@ class Generator(nn.Module):
                      input_is_latent=False, **kw):
         """The mesh of the face of ``styles`` (one face) from narrow-band bricks: the
         mapping network and truncation of ``query_field``, then ``mesh.extract_mesh_sparse``
-        (``kw``: level, lipschitz, grow, return_volume) -> ``Mesh``."""
+        (``kw``: level, lipschitz, grow, return_volume, components -- e.g.
+        ``components={"largest": 1}`` keeps the largest connected component) -> ``Mesh``."""
         from .mesh import extract_mesh_sparse
         lat0 = self._renderer_latent(styles, truncation, truncation_latent, input_is_latent)
         return extract_mesh_sparse(self.renderer, lat0, res=res, **kw)

@@ -24,8 +24,17 @@ dense cube: the field on the 8^3-point bricks near the surface only, marching cu
 that storage (csrc/mesh_sparse.hip), growth along the surface into bricks the first guess
 missed -- up to 1024^3.  ``sparse_extract`` is the driver for any field, ``SparseVolume``
 what it stored.
+
+``mesh_components`` / ``keep_components`` split a mesh into its connected components and keep
+the wanted ones on the GPU (csrc/mesh_cc.hip, ``sdfr_mesh_cc_*``): the field's mesh is the
+face plus whatever the untrained space outside the camera frustum holds, and
+``keep_components(mesh, largest=1)`` -- or ``extract_mesh_sparse(..., components={"largest":
+1})``, before the copy to the host -- is what trimesh's ``mesh.split()`` is used for.
 """
 from __future__ import annotations
+
+import ctypes
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -68,7 +77,8 @@ class Mesh:
     """Indexed triangle mesh: ``vertices`` [V, 3] float32, ``faces`` [F, 3] int64
     (counter-clockwise about the outward normal).  Stands in for the
     ``trimesh.Trimesh`` the reference returns; trimesh's merge / cleanup
-    processing is not applied (vertices are already unique per grid edge)."""
+    processing is not applied (vertices are already unique per grid edge);
+    ``mesh_components`` / ``keep_components`` stand in for ``split()``."""
 
     def __init__(self, vertices, faces, vertex_colors=None, vertex_normals=None):
         self.vertices = np.asarray(vertices, np.float32)
@@ -311,8 +321,235 @@ def sparse_extract(evaluate, axes, res: int, seeds: torch.Tensor, level: float =
     return verts, faces, volume
 
 
+Components = namedtuple("Components", ("comp", "n_vertices", "n_faces", "bbox", "area", "count"))
+Components.__doc__ = """The connected components of a mesh (``mesh_components``): ``comp`` [V]
+int32, the dense id of every vertex's component -- ids 0..count-1 in increasing order of the
+component's smallest vertex index; per component ``n_vertices`` and ``n_faces`` [C] int64,
+``bbox`` [C, 6] fp32 (min x y z, max x y z over its vertices) and ``area`` [C] float64."""
+
+_SELECTORS = ("keep", "largest", "min_faces", "min_area_frac")
+
+
+def _cc_check(rc: int, what: str):
+    """``_lib.check``, with the device-side findings (a bad face index) as ValueError."""
+    from . import _lib
+    if rc == _lib.SDFR_EINVAL:
+        msg = _lib.lib().sdfr_last_error().decode(errors="replace")
+        if "outside [0," in msg:
+            raise ValueError(f"{what}: {msg}")
+    _lib.check(rc, what)
+
+
+def _cc_inputs(what, mesh_or_verts, faces):
+    """-> (verts [V, 3] fp32 GPU, faces [F, 3] int32 GPU, the Mesh or None)."""
+    mesh = mesh_or_verts if isinstance(mesh_or_verts, Mesh) else None
+    if mesh is not None:
+        if faces is not None:
+            raise ValueError(f"{what}: give a Mesh, or vertices and faces")
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{what}: needs the GPU (HIP kernels)")
+        verts = torch.from_numpy(mesh.vertices).to("cuda")
+        faces = torch.from_numpy(mesh.faces).to("cuda")
+    else:
+        verts = mesh_or_verts
+        if not torch.is_tensor(verts) or not torch.is_tensor(faces):
+            raise ValueError(f"{what}: give a Mesh, or vertices and faces as tensors")
+        if not verts.is_cuda or not faces.is_cuda:
+            raise RuntimeError(f"{what}: vertices and faces must be on the GPU (HIP kernels)")
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
+        raise ValueError(f"{what}: vertices must be [V, 3] with V >= 1, got {tuple(verts.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: faces must be [F, 3], got {tuple(faces.shape)}")
+    V, F = verts.shape[0], faces.shape[0]
+    if V >= 2 ** 31 or 3 * F >= 2 ** 31:
+        raise ValueError(f"{what}: V and 3 F must be below 2^31")
+    if faces.dtype == torch.int64:
+        if F:
+            lo, hi = (int(x) for x in faces.aminmax())
+            if lo < 0 or hi >= V:
+                raise ValueError(f"{what}: a face index is outside [0, V) ({lo} .. {hi}, V = {V})")
+        faces = faces.to(torch.int32)
+    elif faces.dtype != torch.int32:
+        raise ValueError(f"{what}: faces must be int32 or int64, not {faces.dtype}")
+    return verts.to(torch.float32).contiguous(), faces.contiguous(), mesh
+
+
+def _cc_workspace(verts, faces):
+    from . import _lib
+    n = _lib.lib().sdfr_mesh_cc_workspace_bytes(verts.shape[0], faces.shape[0])
+    return torch.empty(n, dtype=torch.uint8, device=verts.device), n
+
+
+def label_components(faces: torch.Tensor, n_vertices: int):
+    """``(label [V] int32, comp [V] int32, count)`` of the faces [F, 3] int32 (GPU) of a mesh
+    with ``n_vertices`` vertices (``sdfr_mesh_cc_label``, csrc/mesh_cc.hip): ``label[v]`` is the
+    smallest vertex index of v's component, ``comp[v]`` its dense id (components in increasing
+    order of their smallest vertex).  Both are pure functions of the mesh.  ValueError for a
+    face index outside [0, V): the kernel skips such a face, it is never dereferenced."""
+    from . import _lib
+    V, F = int(n_vertices), faces.shape[0]
+    L = _lib.lib()
+    n = L.sdfr_mesh_cc_workspace_bytes(V, F)
+    ws = torch.empty(n, dtype=torch.uint8, device=faces.device)
+    label = torch.empty(V, dtype=torch.int32, device=faces.device)
+    comp = torch.empty(V, dtype=torch.int32, device=faces.device)
+    count = _lib._u32(0)
+    _cc_check(L.sdfr_mesh_cc_label(_lib.ptr(faces), V, F, _lib.ptr(label), _lib.ptr(comp),
+                                   _lib.ptr(ws), n, count, _lib.stream_of(faces)),
+              "label_components")
+    return label, comp, int(count.value)
+
+
+def component_stats(verts: torch.Tensor, faces: torch.Tensor, comp: torch.Tensor, count: int):
+    """``(n_vertices [C] int32, n_faces [C] int32, bbox [C, 6] fp32, area_q [C] int64, unit)``
+    of the components ``comp`` / ``count`` of ``label_components`` (``sdfr_mesh_cc_stats``):
+    integer atomics only, so every tensor is reproducible bit for bit.  The area of component
+    c is ``area_q[c] * unit`` (unsigned fixed point, below 2^62, in an int64 tensor); ``unit``
+    is the power of two include/sdfr.h derives from the bounding box and F, and
+    ``|area_q[c] * unit - exact| <= n_faces[c] * unit / 2 + 2^11 * unit``."""
+    from . import _lib
+    L = _lib.lib()
+    dev = verts.device
+    V, F, C = verts.shape[0], faces.shape[0], int(count)
+    ws, n = _cc_workspace(verts, faces)
+    nv = torch.empty(C, dtype=torch.int32, device=dev)
+    nf = torch.empty(C, dtype=torch.int32, device=dev)
+    bbox = torch.empty(C, 6, dtype=torch.float32, device=dev)
+    area_q = torch.empty(C, dtype=torch.int64, device=dev)
+    unit = ctypes.c_double(0.0)
+    _cc_check(L.sdfr_mesh_cc_stats(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(comp), V, F, C,
+                                   _lib.ptr(nv), _lib.ptr(nf), _lib.ptr(bbox), _lib.ptr(area_q),
+                                   unit, _lib.ptr(ws), n, _lib.stream_of(verts)),
+              "component_stats")
+    return nv, nf, bbox, area_q, float(unit.value)
+
+
+def _components(verts, faces):
+    _, comp, count = label_components(faces, verts.shape[0])
+    nv, nf, bbox, area_q, unit = component_stats(verts, faces, comp, count)
+    return Components(comp, nv.long(), nf.long(), bbox, area_q.double() * unit, count)
+
+
+def mesh_components(mesh_or_verts, faces=None) -> Components:
+    """The connected components of a triangle mesh, on the GPU (csrc/mesh_cc.hip: a lock-free
+    union-find over the face edges, then integer-atomic statistics) -- what users of the
+    reference get from trimesh's ``mesh.split()``.  A ``Mesh`` (host arrays: moved to the GPU,
+    results as NumPy arrays), or ``verts`` [V, 3] fp32 and ``faces`` [F, 3] int32 | int64 on
+    the GPU (results stay there).  Two vertices are connected when a face references both; a
+    vertex no face references is a component of its own with 0 faces.  Ids run in increasing
+    order of the components' smallest vertex index, and every result is reproducible bit for
+    bit.  ValueError for a face index outside [0, V) (or an int64 one that does not fit);
+    there is no CPU path."""
+    verts, faces, mesh = _cc_inputs("mesh_components", mesh_or_verts, faces)
+    c = _components(verts, faces)
+    if mesh is None:
+        return c
+    return Components(*(t.cpu().numpy() for t in c[:5]), c.count)
+
+
+def _keep_mask(c: Components, keep, largest, min_faces, min_area_frac, by):
+    dev = c.comp.device
+    if keep is not None:
+        keep = torch.as_tensor(keep).to(dev)
+        if keep.shape != (c.count,):
+            raise ValueError(f"keep_components: keep must be [C] = [{c.count}], got "
+                             f"{tuple(keep.shape)}")
+        return keep.ne(0)
+    if largest is not None:
+        k = int(largest)
+        if k < 1:
+            raise ValueError("keep_components: largest must be >= 1")
+        size = c.area if by == "area" else c.n_faces
+        order = torch.sort(size, descending=True, stable=True).indices   # ties: lower id first
+        mask = torch.zeros(c.count, dtype=torch.bool, device=dev)
+        mask[order[:k]] = True
+        return mask
+    if min_faces is not None:
+        return c.n_faces >= int(min_faces)
+    return c.area >= float(min_area_frac) * c.area.sum()
+
+
+def keep_components(mesh_or_verts, faces=None, *, keep=None, largest=None, min_faces=None,
+                    min_area_frac=None, by="area", drop_unreferenced=True):
+    """The mesh without the components that are not wanted, compacted on the GPU
+    (``sdfr_mesh_cc_select_count`` / ``_emit``).  Exactly one selector: ``keep`` (bool [C], by
+    the ids of ``mesh_components``), ``largest=k`` (the k largest by ``by``: "area" or
+    "faces"; ties go to the lower id), ``min_faces`` (components with at least that many
+    faces) or ``min_area_frac`` (with at least that fraction of the total area).
+    ``drop_unreferenced`` also drops the vertices of kept components that no face references.
+    Kept vertices and faces keep their original relative order, so keeping everything on a
+    mesh without unreferenced vertices returns arrays equal to the input.
+
+    A ``Mesh`` gives a new ``Mesh`` with ``vertex_colors`` / ``vertex_normals`` carried along;
+    GPU tensors give ``(verts [V', 3], faces [F', 3] int32, index_map [V'] int32)``, all on
+    the GPU, ``index_map`` new -> old vertex.  ValueError when nothing would be kept."""
+    from . import _lib
+    given = [n for n, v in zip(_SELECTORS, (keep, largest, min_faces, min_area_frac))
+             if v is not None]
+    if len(given) != 1:
+        raise ValueError("keep_components: give exactly one of keep, largest, min_faces, "
+                         f"min_area_frac (got {', '.join(given) or 'none'})")
+    if by not in ("area", "faces"):
+        raise ValueError(f"keep_components: by must be 'area' or 'faces', not {by!r}")
+    if keep is not None:
+        # (C is known only after the labelling; a mesh has between 1 and V components)
+        n_verts = len(mesh_or_verts.vertices if isinstance(mesh_or_verts, Mesh)
+                      else mesh_or_verts)
+        shape = tuple(keep.shape) if torch.is_tensor(keep) else np.asarray(keep).shape
+        if len(shape) != 1 or not 1 <= shape[0] <= max(n_verts, 1):
+            raise ValueError("keep_components: keep must be [C], one entry per component (at "
+                             f"most V = {n_verts}), got shape {shape}")
+    verts, faces, mesh = _cc_inputs("keep_components", mesh_or_verts, faces)
+    c = _components(verts, faces)
+    mask = _keep_mask(c, keep, largest, min_faces, min_area_frac, by)
+    if not bool(mask.any()):
+        raise ValueError("keep_components: no component would be kept")
+    mask = mask.to(torch.uint8).contiguous()
+    L = _lib.lib()
+    st = _lib.stream_of(verts)
+    V, F = verts.shape[0], faces.shape[0]
+    ws, n = _cc_workspace(verts, faces)
+    counts = (_lib._u32 * 2)()
+    _cc_check(L.sdfr_mesh_cc_select_count(_lib.ptr(faces), _lib.ptr(c.comp), _lib.ptr(mask), V, F,
+                                          c.count, int(bool(drop_unreferenced)), _lib.ptr(ws), n,
+                                          counts, st), "keep_components")
+    nv, nf = int(counts[0]), int(counts[1])
+    if nv == 0:
+        raise ValueError("keep_components: no vertex would be kept")
+    out_v = torch.empty(nv, 3, dtype=torch.float32, device=verts.device)
+    out_f = torch.empty(nf, 3, dtype=torch.int32, device=verts.device)
+    index_map = torch.empty(nv, dtype=torch.int32, device=verts.device)
+    _cc_check(L.sdfr_mesh_cc_select_emit(_lib.ptr(verts), _lib.ptr(faces), V, F, nv, nf,
+                                         _lib.ptr(ws), n, _lib.ptr(out_v), _lib.ptr(out_f),
+                                         _lib.ptr(index_map), st), "keep_components")
+    if mesh is None:
+        return out_v, out_f, index_map
+    im = index_map.cpu().numpy()
+    return Mesh(out_v.cpu().numpy(), out_f.cpu().numpy(),
+                None if mesh.vertex_colors is None else mesh.vertex_colors[im],
+                None if mesh.vertex_normals is None else mesh.vertex_normals[im])
+
+
+def sparse_mesh(evaluate, axes, res: int, seeds: torch.Tensor, level: float = 0.0,
+                grow: bool = True, components=None):
+    """``sparse_extract`` and ``extract_mesh_sparse``'s finish: ``(Mesh, SparseVolume)`` with
+    the vertices scaled to (v / res - 0.5) * 0.24 per axis and y, z negated, on the host.
+    ``components``: ``None``, or a dict of ``keep_components`` keyword arguments that filters
+    the mesh on the GPU before the scaling and before the copy to the host (so only what is
+    kept is copied)."""
+    verts, faces, volume = sparse_extract(evaluate, axes, res, seeds, level, grow)
+    if components is not None:
+        verts, faces, _ = keep_components(verts, faces, **components)
+    for axis in range(3):
+        verts[:, axis] = (verts[:, axis] / float(res) - 0.5) * 0.24
+    verts[:, 2] *= -1
+    verts[:, 1] *= -1
+    return Mesh(verts.cpu().numpy(), faces.cpu().numpy()), volume
+
+
 def extract_mesh_sparse(renderer, styles: torch.Tensor, res: int = 512, level: float = 0.0,
-                        lipschitz=None, grow: bool = True, return_volume: bool = False):
+                        lipschitz=None, grow: bool = True, return_volume: bool = False,
+                        components=None):
     """The ``level`` set of the field itself at ``res``^3 without the dense cube: the
     ``Mesh`` that ``extract_mesh_with_marching_cubes(sdf_cube(renderer, styles, res))``
     gives (same vertex scaling and y / z flips, the same triangles with bit-equal
@@ -330,7 +567,13 @@ def extract_mesh_sparse(renderer, styles: torch.Tensor, res: int = 512, level: f
     be a seed.  With ``grow`` every surface component that touches a seed brick is still
     extracted completely, whatever L is; what can be missed is a component that lies
     entirely inside skipped bricks (a small detached blob far from where the SDF is
-    small at the centres).  ``return_volume``: also the ``SparseVolume``."""
+    small at the centres).  ``return_volume``: also the ``SparseVolume``.
+
+    ``components``: ``None`` (everything found), or a dict of ``keep_components`` keyword
+    arguments, e.g. ``{"largest": 1}``: the mesh is split into its connected components and
+    filtered on the GPU before the vertex scaling and before the copy to the host, so the
+    unwanted components are never copied.  The components' bounding boxes and areas then
+    refer to index coordinates (0 .. res - 1 per axis), not to world coordinates."""
     if styles.shape[0] != 1:
         raise ValueError("extract_mesh_sparse: one mesh, one face (styles [1, 256])")
     nb = _check_brick_res(res, "extract_mesh_sparse")
@@ -353,12 +596,7 @@ def extract_mesh_sparse(renderer, styles: torch.Tensor, res: int = 512, level: f
                               .norm(dim=-1).max())
         band = float(lipschitz) * 4.0 * (3.0 ** 0.5) * (2.0 / res)
         seeds = (sdf_c.reshape(-1).float() - level).abs() <= band
-        verts, faces, volume = sparse_extract(evaluate, axes, res, seeds, level, grow)
-    for axis in range(3):
-        verts[:, axis] = (verts[:, axis] / float(res) - 0.5) * 0.24
-    verts[:, 2] *= -1
-    verts[:, 1] *= -1
-    mesh = Mesh(verts.cpu().numpy(), faces.cpu().numpy())
+        mesh, volume = sparse_mesh(evaluate, axes, res, seeds, level, grow, components)
     return (mesh, volume) if return_volume else mesh
 
 
