@@ -9,7 +9,7 @@ and double-backward structure.  A missing libsdfr.so raises; there is no
 silent PyTorch substitute on the GPU.
 
 ``styled_epilogue`` / ``modulate_to_nhwc`` are the fused decoder pieces used
-by ``Decoder`` on its inference path (see generator.py).
+by ``Decoder`` on its inference path (see decoder_fused.py).
 """
 from __future__ import annotations
 
@@ -237,6 +237,43 @@ def separable_taps(kernel_2d):
     return None
 
 
+def _split_dims(x_split, what):
+    """(B, H, W, Cin) of a split-NHWC argument [B,H,W,Cin/8,2,8], checked."""
+    _require_cuda(x_split)
+    if x_split.dtype != torch.float16 or x_split.dim() != 6 or x_split.shape[4:] != (2, 8) \
+            or not x_split.is_contiguous():
+        raise RuntimeError(f"{what}: x_split must be a contiguous split-NHWC fp16 "
+                           "tensor [B,H,W,Cin/8,2,8]")
+    return x_split.shape[0], x_split.shape[1], x_split.shape[2], 8 * x_split.shape[3]
+
+
+def _cptr(t, keep):
+    """Device pointer of ``t`` made contiguous (None -> NULL); the contiguous tensor joins
+    ``keep``, which the caller holds until its launch is enqueued."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    keep.append(t)
+    return _lib.ptr(t)
+
+
+def _set_epilogue(a, keep, out_shape, *, demod, noise, noise_weight, bias, negative_slope,
+                  act_scale, s_next, y_split):
+    """The epilogue members that sdfr_styled_epilogue_args, sdfr_conv_act_args and
+    sdfr_conv_t_act_args share, set on ``a``; ``out_shape`` = (B, H, W) of the epilogue's
+    output, to which a shared noise map [1,1,H,W] is expanded."""
+    if noise is not None:
+        B, H, W = out_shape
+        noise = noise.expand(B, 1, H, W)
+    a.demod = _cptr(demod, keep)
+    a.noise = _cptr(noise, keep)
+    a.noise_weight = _cptr(noise_weight, keep)
+    a.bias = _cptr(bias.reshape(-1), keep)
+    a.negative_slope, a.act_scale = negative_slope, act_scale
+    a.s_next = _cptr(s_next, keep)
+    a.y_split = _lib.ptr(y_split)
+
+
 def modulate_to_nhwc(x, s):
     """x [B,C,H,W] (NCHW) * s[b,c] -> channels_last [B,C,H,W]."""
     _require_cuda(x, s)
@@ -267,36 +304,20 @@ def styled_epilogue(conv, *, fir, bias, noise_weight, noise=None, demod=None, bl
     if store_y and split_y:
         ys = torch.empty(B, H, W, C // 8, 2, 8, device=conv.device, dtype=torch.float16)
     rgb = torch.empty(B, 3, H, W, device=conv.device) if rgb_w is not None else None
-    if noise is not None:
-        noise = noise.expand(B, 1, H, W).contiguous()
     a = _lib.StyledEpilogueArgs()
     a.B, a.C, a.H, a.W = B, C, H, W
     a.conv = _lib.ptr(conv)
     a.blur_up = int(blur_up)
-    for i in range(4):
-        a.fir[i] = fir[i]
+    a.fir[:] = fir
     keep = []
-
-    def cptr(t):
-        if t is None:
-            return None
-        t = t.contiguous()
-        keep.append(t)
-        return _lib.ptr(t)
-
-    a.demod = cptr(demod)
-    a.noise = cptr(noise)
-    a.noise_weight = cptr(noise_weight)
-    a.bias = cptr(bias.reshape(-1))
-    a.negative_slope = negative_slope
-    a.act_scale = act_scale
-    a.s_next = cptr(s_next)
+    _set_epilogue(a, keep, (B, H, W), demod=demod, noise=noise, noise_weight=noise_weight,
+                  bias=bias, negative_slope=negative_slope, act_scale=act_scale,
+                  s_next=s_next, y_split=ys)
     a.y = _lib.ptr(y)
-    a.rgb_w = cptr(rgb_w)
-    a.rgb_b = cptr(None if rgb_b is None else rgb_b.reshape(-1))
-    a.skip = cptr(skip)
+    a.rgb_w = _cptr(rgb_w, keep)
+    a.rgb_b = _cptr(None if rgb_b is None else rgb_b.reshape(-1), keep)
+    a.skip = _cptr(skip, keep)
     a.rgb = _lib.ptr(rgb)
-    a.y_split = _lib.ptr(ys)
     _lib.check(_lib.lib().sdfr_styled_epilogue(a, _lib.stream_of(conv)), "styled_epilogue")
     return (ys if split_y and store_y else y), rgb
 
@@ -342,12 +363,7 @@ def conv3x3_f16x3(x_split, packed, Cout, transposed=False, split_k=True):
     stride 2), scaled by su (conv_pack_weights).  ``split_k``: give the kernel a
     workspace so that small batches split K over 2-4 workgroups
     (sdfr_conv3x3_f16x3_ws)."""
-    _require_cuda(x_split)
-    if x_split.dtype != torch.float16 or x_split.dim() != 6 or x_split.shape[4:] != (2, 8) \
-            or not x_split.is_contiguous():
-        raise RuntimeError("conv3x3_f16x3: x_split must be a contiguous split-NHWC fp16 "
-                           "tensor [B,H,W,Cin/8,2,8]")
-    B, H, W, Cin = x_split.shape[0], x_split.shape[1], x_split.shape[2], 8 * x_split.shape[3]
+    B, H, W, Cin = _split_dims(x_split, "conv3x3_f16x3")
     Ho, Wo = (2 * H + 1, 2 * W + 1) if transposed else (H, W)
     out = torch.empty(B, Cout, Ho, Wo, device=x_split.device, memory_format=torch.channels_last)
     wsb = _lib.lib().sdfr_conv_ws_bytes(B, H, W, Cout, int(bool(transposed))) if split_k else 0
@@ -371,41 +387,22 @@ def conv3x3_f16x3_act(x_split, packed, Cout, *, demod, bias, noise_weight, noise
     [B,Cout] multiplied in the kernel (the same fp32 products, one launch less)."""
     if rgb_w is not None and rgb_base is not None:
         raise RuntimeError("conv3x3_f16x3_act: rgb_w and rgb_base are exclusive")
-    _require_cuda(x_split)
-    if x_split.dtype != torch.float16 or x_split.dim() != 6 or x_split.shape[4:] != (2, 8) \
-            or not x_split.is_contiguous():
-        raise RuntimeError("conv3x3_f16x3_act: x_split must be a contiguous split-NHWC fp16 "
-                           "tensor [B,H,W,Cin/8,2,8]")
-    B, H, W, Cin = x_split.shape[0], x_split.shape[1], x_split.shape[2], 8 * x_split.shape[3]
+    B, H, W, Cin = _split_dims(x_split, "conv3x3_f16x3_act")
     dev = x_split.device
     ys = (torch.empty(B, H, W, Cout // 8, 2, 8, device=dev, dtype=torch.float16)
           if store_y else None)
     rgb = rgb_w is not None or rgb_base is not None
     part = torch.empty(Cout // 128, B, 3, H, W, device=dev) if rgb else None
-    if noise is not None:
-        noise = noise.expand(B, 1, H, W).contiguous()
     keep = []
-
-    def cptr(t):
-        if t is None:
-            return None
-        t = t.contiguous()
-        keep.append(t)
-        return _lib.ptr(t)
-
     a = _lib.ConvActArgs()
     a.x_split, a.packed = _lib.ptr(x_split), _lib.ptr(packed)
     a.B, a.H, a.W, a.Cin, a.Cout = B, H, W, Cin, Cout
-    a.demod = cptr(demod)
-    a.noise = cptr(noise)
-    a.noise_weight = cptr(noise_weight)
-    a.bias = cptr(bias.reshape(-1))
-    a.negative_slope, a.act_scale = negative_slope, act_scale
-    a.s_next = cptr(s_next)
-    a.y_split = _lib.ptr(ys)
-    a.rgb_w = cptr(rgb_w)
-    a.rgb_base = cptr(rgb_base)
-    a.rgb_s = cptr(rgb_s)
+    _set_epilogue(a, keep, (B, H, W), demod=demod, noise=noise, noise_weight=noise_weight,
+                  bias=bias, negative_slope=negative_slope, act_scale=act_scale,
+                  s_next=s_next, y_split=ys)
+    a.rgb_w = _cptr(rgb_w, keep)
+    a.rgb_base = _cptr(rgb_base, keep)
+    a.rgb_s = _cptr(rgb_s, keep)
     a.rgb_partial = _lib.ptr(part)
     wsb = _lib.lib().sdfr_conv_act_ws_bytes(B, H, W, Cout) if split_k else 0
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
@@ -427,38 +424,18 @@ def conv_t_act(x_split, packed, Cout, *, fir, demod, bias, noise_weight, noise=N
     (sdfr_conv_t_act): returns y split-NHWC [B,2H,2W,Cout/8,2,8] fp16 -- the same bits
     as conv3x3_f16x3(transposed=True) followed by styled_epilogue(blur_up=True,
     split_y=True).  demod must already carry 1/su."""
-    _require_cuda(x_split)
-    if x_split.dtype != torch.float16 or x_split.dim() != 6 or x_split.shape[4:] != (2, 8) \
-            or not x_split.is_contiguous():
-        raise RuntimeError("conv_t_act: x_split must be a contiguous split-NHWC fp16 "
-                           "tensor [B,H,W,Cin/8,2,8]")
-    B, H, W, Cin = x_split.shape[0], x_split.shape[1], x_split.shape[2], 8 * x_split.shape[3]
+    B, H, W, Cin = _split_dims(x_split, "conv_t_act")
     dev = x_split.device
     ys = torch.empty(B, 2 * H, 2 * W, Cout // 8, 2, 8, device=dev, dtype=torch.float16)
     raw = torch.empty(B, 2 * H + 1, 2 * W + 1, Cout, device=dev)
-    if noise is not None:
-        noise = noise.expand(B, 1, 2 * H, 2 * W).contiguous()
     keep = []
-
-    def cptr(t):
-        if t is None:
-            return None
-        t = t.contiguous()
-        keep.append(t)
-        return _lib.ptr(t)
-
     a = _lib.ConvTActArgs()
     a.x_split, a.packed = _lib.ptr(x_split), _lib.ptr(packed)
     a.B, a.H, a.W, a.Cin, a.Cout = B, H, W, Cin, Cout
-    for i in range(4):
-        a.fir[i] = fir[i]
-    a.demod = cptr(demod)
-    a.noise = cptr(noise)
-    a.noise_weight = cptr(noise_weight)
-    a.bias = cptr(bias.reshape(-1))
-    a.negative_slope, a.act_scale = negative_slope, act_scale
-    a.s_next = cptr(s_next)
-    a.y_split = _lib.ptr(ys)
+    a.fir[:] = fir
+    _set_epilogue(a, keep, (B, 2 * H, 2 * W), demod=demod, noise=noise,
+                  noise_weight=noise_weight, bias=bias, negative_slope=negative_slope,
+                  act_scale=act_scale, s_next=s_next, y_split=ys)
     a.raw = _lib.ptr(raw)
     _lib.check(_lib.lib().sdfr_conv_t_act(a, _lib.stream_of(x_split)), "conv_t_act")
     return ys

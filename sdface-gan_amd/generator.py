@@ -6,12 +6,14 @@ Follows im2scene/sdf/models/sdf_model.py:
   ToRGB :821-843           Decoder :883-1056         Generator :1059-1216
 and the device-agnostic forms of the fused ops of sdf_op.py:105-120 / 259-314.
 
-The decoder's convolutions stay on MIOpen.  Its modulated
-convolution runs as ``conv(x * s, W) * demod`` -- one batched convolution
-instead of the reference's per-face grouped convolution (same algebra, fp32).
-On the GPU, the bias/leaky-ReLU and upfirdn2d ops are the HIP kernels of
-decoder_ops.py; at inference (no grad) everything between two convolutions is
-one HIP epilogue over channels_last activations (``Decoder._fused_forward``).
+The decoder's modulated convolution runs as ``conv(x * s, W) * demod`` -- one
+batched convolution instead of the reference's per-face grouped convolution
+(same algebra, fp32); on the module path that convolution is MIOpen's.  On the
+GPU, the bias/leaky-ReLU and upfirdn2d ops are the HIP kernels of
+decoder_ops.py; at inference (no grad) the convolutions are the split-fp16
+MFMA kernels of csrc/conv_f16x3.hip and everything between two of them is one
+HIP epilogue, inside the conv kernel where it can be (decoder_fused.py:
+``FusedDecoder``, which ``Decoder`` inherits).
 
 Geometry-aware noise projection (``Generator.forward(project_noise=True, mesh_path=...)``
 on a model built with ``project_noise``; the reference rasterises with pytorch3d) runs on
@@ -35,10 +37,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .decoder_ops import (conv3x3_f16x3, conv3x3_f16x3_act, conv_pack_weights,  # noqa: E402
-                          conv_t_act, conv_t_act_supported, modulate_to_nhwc_split, rgb_finish)
-from .decoder_ops import (FusedLeakyReLU, fused_leaky_relu, modulate_to_nhwc,  # noqa: F401
-                          separable_taps, styled_epilogue, upfirdn2d)
+from .decoder_fused import FusedDecoder
+from .decoder_ops import FusedLeakyReLU, fused_leaky_relu, upfirdn2d  # noqa: F401
 from .renderer import VolumeFeatureRenderer
 
 
@@ -48,8 +48,6 @@ def make_kernel(k):
         k = k[None, :] * k[:, None]
     return k / k.sum()
 
-
-_EMPTY = {}                      # device -> a 0-element tensor (fused_ready's probe)
 
 class Upsample(nn.Module):
     def __init__(self, kernel, factor=2):
@@ -374,8 +372,10 @@ class ToRGB(nn.Module):
         return out
 
 
-class Decoder(nn.Module):
-    """StyleGAN2 2D decoder, 64^2 x 256 features -> size^2 RGB (sdf_model.py:883-1056)."""
+class Decoder(FusedDecoder, nn.Module):
+    """StyleGAN2 2D decoder, 64^2 x 256 features -> size^2 RGB (sdf_model.py:883-1056).
+    Its fused inference path (``fused_ready``, ``prepare_fused``, ``_fused_forward``) is
+    decoder_fused.FusedDecoder."""
 
     def __init__(self, model_opt, blur_kernel=(1, 3, 3, 1)):
         super().__init__()
@@ -442,10 +442,7 @@ class Decoder(nn.Module):
         self.conv_events = None
         self.conv_flops = 0
         self._conv_ev = 0
-        self._fir = None
-        self._packs = {}
-        self._mod_stack = None
-        self._demod_stack = None
+        self._plan = None          # decoder_fused.DecoderPlan of the current weights
 
     def mean_latent(self, renderer_latent):
         return self.style(renderer_latent).mean(0, keepdim=True)
@@ -503,23 +500,19 @@ class Decoder(nn.Module):
     def forward(self, features, styles, rgbd_in=None, transform=None, return_latents=False,
                 inject_index=None, truncation=1, truncation_latent=None, input_is_latent=False,
                 noise=None, randomize_noise=True, mesh_path=None, prepared=None, focal=None):
-        if self._projects(transform):
-            # projected noise: the maps are formed up front (one rasterisation per
-            # resolution, shared by its layers), and the decoder then runs as it does
-            # without a transform -- through the fused path where that applies
-            if mesh_path is None:
-                raise ValueError("Decoder: project_noise needs a mesh_path")
-            self._proj.rasters = {}
-            try:
-                return self._forward(features, styles, rgbd_in, transform, return_latents,
-                                     inject_index, truncation, truncation_latent,
-                                     input_is_latent, noise, randomize_noise, mesh_path,
-                                     prepared, focal)
-            finally:
-                self._proj.rasters = None
-        return self._forward(features, styles, rgbd_in, transform, return_latents,
-                             inject_index, truncation, truncation_latent, input_is_latent,
-                             noise, randomize_noise, mesh_path, prepared, focal)
+        # projected noise: the maps are formed up front (one rasterisation per
+        # resolution, shared by its layers while this call runs), and the decoder then
+        # runs as it does without a transform -- through the fused path where that applies
+        projects = self._projects(transform)
+        if projects and mesh_path is None:
+            raise ValueError("Decoder: project_noise needs a mesh_path")
+        self._proj.rasters = {} if projects else None
+        try:
+            return self._forward(features, styles, rgbd_in, transform, return_latents,
+                                 inject_index, truncation, truncation_latent, input_is_latent,
+                                 noise, randomize_noise, mesh_path, prepared, focal)
+        finally:
+            self._proj.rasters = None
 
     def _forward(self, features, styles, rgbd_in, transform, return_latents, inject_index,
                  truncation, truncation_latent, input_is_latent, noise, randomize_noise,
@@ -555,383 +548,6 @@ class Decoder(nn.Module):
             skip = to_rgb(out, latent[:, i + 2], skip=skip)
             i += 2
         return skip, (latent if return_latents else None)
-
-    # -- fused inference path ------------------------------------------------
-    def _fused_ok(self, features, rgbd_in, transform):
-        if not (self.use_fused and features.is_cuda and rgbd_in is None and transform is None):
-            return False
-        if torch.is_grad_enabled() and (features.requires_grad or
-                                        any(p.requires_grad for p in self.parameters())):
-            return False
-        if self._fir is None:
-            fir = separable_taps(self.convs[0].conv.blur.kernel) if len(self.convs) else [0.0] * 4
-            ok = fir is not None and all(
-                torch.equal(t.upsample.kernel.cpu(), self.convs[0].conv.blur.kernel.cpu())
-                for t in self.to_rgbs)
-            self._fir = fir if ok else False
-        return self._fir is not False
-
-    def fused_ready(self, device, transform=None, rgbd_in=None):
-        """Will forward() take the fused path for features on ``device``?  (Checked
-        before the features exist, so that prepare_fused can run beside the renderer.)"""
-        if device.type != "cuda":
-            return False
-        probe = _EMPTY.get(device)
-        if probe is None:
-            probe = _EMPTY[device] = torch.empty(0, device=device)
-        return self._fused_ok(probe, rgbd_in, transform)
-
-    def prepare_fused(self, styles, B, device, noise=None, inject_index=None, truncation=1,
-                      truncation_latent=None, input_is_latent=False, randomize_noise=True):
-        """Everything of the fused forward that does not depend on the features: the
-        mapping network, the noise maps and every layer's modulation / demodulation;
-        forward(..., prepared=<this>) then runs the convolutions.  The same work, in
-        the same order, as forward() does it."""
-        latent, noise = self.styles_and_noise_forward(styles, noise, inject_index, truncation,
-                                                      truncation_latent, input_is_latent,
-                                                      randomize_noise)
-        seq = [self.conv1] + list(self.convs)
-        noise = self._fused_noise(noise, B, device, torch.float32)
-        split = [self._conv_x(sc.conv) for sc in seq]
-        return latent, noise, self._fused_styles(latent, seq, split)
-
-    def _fused_styles(self, latent, seq, split):
-        if latent.is_cuda and latent.dtype == torch.float32 and self.style_dim in (256, 512):
-            return self._styles_fused(latent, seq, split)
-        mods, rgb_mods, mods_raw = self._modulations(latent)
-        return mods, rgb_mods, self._demods(seq, split, mods_raw)
-
-    def _conv_x(self, mc):
-        """Does this ModulatedConv2d run on the split-fp16 implicit GEMM?"""
-        _, cout, cin, k, _ = mc.weight.shape
-        return (self.conv_impl == "f16x3" and k == 3 and mc.demodulate and not mc.downsample
-                and cout % 128 == 0 and cin % 32 == 0)
-
-    def _pack(self, i, mc):
-        """Per weight version of layer i: the packed split-fp16 weights, their row
-        scales su and, for the demodulation, su^2 * sum_{ky,kx} w^2 as [Cin, Cout]
-        plus su^2 * 1e-8: rsqrt(s^2 @ that + that) is demod / su exactly (powers
-        of two commute with rounding), in one GEMM + one rsqrt per call."""
-        key = (mc.weight.data_ptr(), mc.weight._version, mc.weight.device)
-        hit = self._packs.get(i)
-        if hit is None or hit[0] != key:
-            packed, su = conv_pack_weights(mc.weight[0], mc.scale)
-            with torch.no_grad():
-                w = mc.scale * mc.weight[0]
-                s2 = su * su
-                wsq = ((w * w).sum([2, 3]) * s2[:, None]).t().contiguous()
-                eps = s2 * 1e-8
-            hit = (key, packed, su, wsq, eps)
-            self._packs[i] = hit
-        return hit[1:]
-
-    def _modulations(self, latent):
-        """Every conv and ToRGB modulation of the fused path (EqualLinear,
-        sdf_model.py:676-699) as ONE batched GEMM: the 11 weight matrices
-        (x scale, zero-padded to the widest) and biases (x lr_mul) are stacked once
-        per weight version, latent rows gathered per layer; one baddbmm instead of
-        three small kernels per layer.  fp32, summation order of the batched GEMM."""
-        seq = [self.conv1] + list(self.convs)
-        rgbs = [self.to_rgb1] + list(self.to_rgbs)
-        lins = [sc.conv.modulation for sc in seq] + [t.conv.modulation for t in rgbs]
-        key = tuple((m.weight.data_ptr(), m.weight._version, m.bias._version) for m in lins)
-        if self._mod_stack is None or self._mod_stack[0] != key:
-            cmax = max(m.weight.shape[0] for m in lins)
-            w0 = lins[0].weight
-            wt = w0.new_zeros(len(lins), w0.shape[1], cmax)
-            bs = w0.new_zeros(len(lins), 1, cmax)
-            with torch.no_grad():
-                for k, m in enumerate(lins):
-                    c = m.weight.shape[0]
-                    wt[k, :, :c] = (m.weight * m.scale).t()
-                    bs[k, 0, :c] = m.bias * m.lr_mul
-            # latent index per stacked layer: conv i -> i, ToRGB k -> 2k + 1
-            idx = torch.tensor(list(range(len(seq))) + [2 * k + 1 for k in range(len(rgbs))],
-                               device=w0.device)
-            self._mod_stack = (key, wt, bs, idx, [m.weight.shape[0] for m in lins], len(seq))
-        _, wt, bs, idx, cins, nconv = self._mod_stack
-        out = torch.baddbmm(bs, latent.index_select(1, idx).transpose(0, 1), wt)
-        mods = [out[k, :, :c].contiguous() for k, c in enumerate(cins)]
-        return mods[:nconv], mods[nconv:], out[:nconv]
-
-    def _demods(self, seq, split, mods_raw):
-        """demod / su of every split-fp16 layer (see _pack) in one batched GEMM +
-        one rsqrt: the layers' [Cin, Cout] weight sums and eps rows are stacked
-        (zero-padded) once per weight version; mods_raw is _modulations' padded
-        [layers, B, Cmax] output (its padding is exactly 0)."""
-        layers = [i for i, sc in enumerate(seq) if split[i] and sc.conv.demodulate]
-        if not layers:
-            return {}
-        packs = {i: self._pack(i, seq[i].conv) for i in layers}
-        key = tuple(self._packs[i][0] for i in layers)
-        if getattr(self, "_demod_stack", None) is None or self._demod_stack[0] != key:
-            cmax = mods_raw.shape[-1]
-            omax = max(packs[i][2].shape[1] for i in layers)
-            w0 = packs[layers[0]][2]
-            wsq = w0.new_zeros(len(layers), cmax, omax)
-            eps = w0.new_zeros(len(layers), 1, omax)
-            for j, i in enumerate(layers):
-                cin, cout = packs[i][2].shape
-                wsq[j, :cin, :cout] = packs[i][2]
-                eps[j, 0, :cout] = packs[i][3]
-            sel = torch.tensor(layers, device=w0.device)
-            self._demod_stack = (key, wsq, eps, sel)
-        _, wsq, eps, sel = self._demod_stack
-        m = mods_raw.index_select(0, sel)
-        d = torch.rsqrt(torch.baddbmm(eps, m * m, wsq))
-        return {i: d[j, :, :packs[i][2].shape[1]].contiguous() for j, i in enumerate(layers)}
-
-    def _styles_fused(self, latent, seq, split):
-        """_modulations + _demods in two HIP launches (sdfr_decoder_styles): the
-        stacked, scaled weights are built once per weight version; the per-layer
-        modulations and demodulations come back as contiguous slices of two flat
-        buffers.  fp32, fixed summation order (not the batched GEMM's)."""
-        from . import _lib
-        rgbs = [self.to_rgb1] + list(self.to_rgbs)
-        lins = [sc.conv.modulation for sc in seq] + [t.conv.modulation for t in rgbs]
-        nconv = len(seq)
-        key = tuple((m.weight.data_ptr(), m.weight._version, m.bias._version) for m in lins)
-        cache = getattr(self, "_sty_mod", None)
-        if cache is None or cache[0] != key:
-            cmax = max(256, max(m.weight.shape[0] for m in lins))
-            w0 = lins[0].weight
-            mw = w0.new_zeros(len(lins), cmax, w0.shape[1])
-            mb = w0.new_zeros(len(lins), cmax)
-            with torch.no_grad():
-                for k, m in enumerate(lins):
-                    c = m.weight.shape[0]
-                    mw[k, :c] = m.weight * m.scale
-                    mb[k, :c] = m.bias * m.lr_mul
-            idx = list(range(nconv)) + [2 * k + 1 for k in range(len(rgbs))]
-            cache = (key, mw, mb, idx, [m.weight.shape[0] for m in lins], cmax)
-            self._sty_mod = cache
-        _, mw, mb, idx, couts, cmax = cache
-        layers = [i for i, sc in enumerate(seq) if split[i] and sc.conv.demodulate]
-        packs = {i: self._pack(i, seq[i].conv) for i in layers}
-        dkey = tuple(self._packs[i][0] for i in layers)
-        dcache = getattr(self, "_sty_dem", None)
-        if layers and (dcache is None or dcache[0] != dkey):
-            omax = max(packs[i][2].shape[1] for i in layers)
-            w0 = packs[layers[0]][2]
-            dw = w0.new_zeros(len(layers), omax, cmax)
-            de = w0.new_zeros(len(layers), omax)
-            for j, i in enumerate(layers):
-                cin, cout = packs[i][2].shape
-                dw[j, :cout, :cin] = packs[i][2].t()
-                de[j, :cout] = packs[i][3]
-            dcache = (dkey, dw, de, omax)
-            self._sty_dem = dcache
-        B = latent.shape[0]
-        lat = latent.contiguous()
-        a = _lib.StyleArgs()
-        a.B, a.n_latent, a.K, a.latent = B, lat.shape[1], lat.shape[2], _lib.ptr(lat)
-        a.L, a.cmax, a.mod_w, a.mod_b = len(lins), cmax, _lib.ptr(mw), _lib.ptr(mb)
-        offs, off = [], 0
-        for k, c in enumerate(couts):
-            a.mod_index[k], a.mod_c[k], a.mod_off[k] = idx[k], c, off
-            offs.append(off)
-            off += B * c
-        mflat = torch.empty(off, device=lat.device)
-        a.mods = _lib.ptr(mflat)
-        dflat = None
-        if layers:
-            _, dw, de, omax = dcache
-            a.J, a.omax, a.dem_w, a.dem_eps = len(layers), omax, _lib.ptr(dw), _lib.ptr(de)
-            doffs, doff = [], 0
-            for j, i in enumerate(layers):
-                cout = packs[i][2].shape[1]
-                a.dem_layer[j], a.dem_c[j], a.dem_off[j] = i, cout, doff
-                doffs.append(doff)
-                doff += B * cout
-            dflat = torch.empty(doff, device=lat.device)
-            a.demods = _lib.ptr(dflat)
-        _lib.check(_lib.lib().sdfr_decoder_styles(a, _lib.stream_of(lat)), "sdfr_decoder_styles")
-        mods = [mflat[o:o + B * c].view(B, c) for o, c in zip(offs, couts)]
-        demods = {}
-        if layers:
-            for j, i in enumerate(layers):
-                cout = packs[i][2].shape[1]
-                demods[i] = dflat[doffs[j]:doffs[j] + B * cout].view(B, cout)
-        return mods[:nconv], mods[nconv:], demods
-
-    def _fused_noise(self, noise, B, device, dtype):
-        """The per-layer noise maps of the fused path: the given ones, and every
-        missing one (randomize_noise) sliced from ONE standard-normal draw of all of
-        their elements, layer after layer -- one launch instead of one per layer (the
-        module path draws each layer's map separately, NoiseInjection, so the two
-        paths' random maps differ; their distribution does not)."""
-        missing = [i for i, n in enumerate(noise) if n is None]
-        if not missing:
-            return noise
-        sizes = [2 ** ((i + 2 * self.log_in_size + 1) // 2) for i in range(self.num_layers)]
-        total = sum(B * sizes[i] * sizes[i] for i in missing)
-        flat = torch.randn(total, device=device, dtype=dtype)
-        out, off = list(noise), 0
-        for i in missing:
-            n = B * sizes[i] * sizes[i]
-            out[i] = flat[off:off + n].view(B, 1, sizes[i], sizes[i])
-            off += n
-        return out
-
-    def _rgb_base(self, tc):
-        """ToRGB's scaled 1x1 weight [3, C] (tc.scale * weight), once per weight version."""
-        key = (tc.weight.data_ptr(), tc.weight._version)
-        cache = getattr(tc, "_sdfr_base", None)
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                cache = (key, tc.scale * tc.weight[0, :, :, 0, 0])
-            tc._sdfr_base = cache
-        return cache[1]
-
-    def profile_convs(self, events):
-        """Record `events[k] = (start, end)` around the k-th fused regular convolution of
-        the next forward (None: stop); `conv_flops` counts their fp32-equivalent FLOPs."""
-        self.conv_events, self._conv_ev, self.conv_flops = events, 0, 0
-
-    @staticmethod
-    def _fused_chunk(features, seq):
-        """Faces per fused call: the largest activation of one face (a layer's input,
-        or its raw output -- (2H+1) x (2W+1) for an upsampling layer -- in 4-byte
-        elements) times the batch stays below 2^31 bytes (the 256^2 decoder: 63 faces)."""
-        h, w = (features.shape[1:3] if features.dim() == 6 else features.shape[2:4])
-        per_face = 0
-        for sc in seq:
-            cout, cin = sc.conv.weight.shape[1], sc.conv.weight.shape[2]
-            per_face = max(per_face, h * w * cin * 4)
-            if sc.conv.upsample:
-                per_face = max(per_face, (2 * h + 1) * (2 * w + 1) * cout * 4)
-                h, w = 2 * h, 2 * w
-            per_face = max(per_face, h * w * cout * 4)
-        return max(1, ((1 << 31) - 1) // per_face)
-
-    @staticmethod
-    def _noise_rows(noise, sl, B):
-        """Faces ``sl`` of the per-layer noise maps: a [B, 1, h, w] map is sliced, a
-        shared [1, 1, h, w] map (the decoder's fixed noise buffers) is kept."""
-        return [n[sl] if n is not None and n.shape[0] == B else n for n in noise]
-
-    @staticmethod
-    def _style_rows(sty, sl):
-        """Faces ``sl`` of _fused_styles' (mods, rgb_mods, demods): every modulation and
-        demodulation is [B, C]."""
-        mods, rgb_mods, demods = sty
-        return ([m[sl] for m in mods], [m[sl] for m in rgb_mods],
-                {i: d[sl] for i, d in demods.items()})
-
-    def _fused_forward(self, features, latent, noise, sty=None):
-        """Same computation as the module path: per layer one split-fp16 convolution
-        (or MIOpen's) plus one sdfr_styled_epilogue on NHWC activations -- for the
-        regular convolutions the epilogue runs inside the conv kernel
-        (sdfr_conv3x3_f16x3_act); each activation is pre-multiplied by the next
-        layer's modulation and the ToRGB layers are folded into the preceding
-        epilogue."""
-        cl = torch.channels_last
-        B = features.shape[0]
-        seq = [self.conv1] + list(self.convs)
-        split = [self._conv_x(sc.conv) for sc in seq]     # layer i's input as hi/lo planes
-        if sty is None:
-            noise = self._fused_noise(noise, B, features.device, features.dtype)
-            sty = self._fused_styles(latent, seq, split)
-        chunk = self._fused_chunk(features, seq)
-        if B > chunk:
-            # the kernels index activations with 32-bit offsets (conv_launch: < 2^31 bytes
-            # per tensor): larger batches run as chunks on the same noise maps and styles
-            n_chunks = -(-B // chunk)
-            chunk = -(-B // n_chunks)                     # balanced: 64 faces -> 2 x 32
-            outs = []
-            for b0 in range(0, B, chunk):
-                sl = slice(b0, min(B, b0 + chunk))
-                outs.append(self._fused_forward(features[sl], latent[sl],
-                                                self._noise_rows(noise, sl, B),
-                                                self._style_rows(sty, sl)))
-            return torch.cat(outs, 0)
-        mods, rgb_mods, demods = sty
-        if features.dtype == torch.float16 and features.dim() == 6:
-            # the renderer wrote features * mods[0] in the split layout already (ABI 12)
-            if not split[0]:
-                raise RuntimeError("decoder: split-NHWC features for a non-split first layer")
-            x = features
-        else:
-            x = (modulate_to_nhwc_split if split[0] else modulate_to_nhwc)(features, mods[0])
-        rgb = None
-        for i, sc in enumerate(seq):
-            mc = sc.conv
-            last = i == len(seq) - 1
-            cout = mc.weight.shape[1]
-            if split[i]:
-                packed, su, wsq, eps = self._pack(i, mc)
-                demod_su = demods[i] if mc.demodulate else 1.0 / su.expand(B, -1)
-            if (self.fuse_conv_act and split[i] and not mc.upsample and (last or split[i + 1])
-                    and (x.shape[1] * x.shape[2]) % 256 == 0):
-                # regular conv with the epilogue fused: the conv output stays on chip
-                H, W = x.shape[1], x.shape[2]
-                n = noise[i]
-                rgb_base = rgb_s = None
-                if i % 2 == 0:
-                    # ToRGB's modulated weight base[o, c] * s[b, c] is formed inside the
-                    # conv's epilogue (the same fp32 products as the module path's
-                    # weight * style, without a [B, 3, C] multiply launch)
-                    to_rgb = self.to_rgb1 if i == 0 else self.to_rgbs[i // 2 - 1]
-                    tc = to_rgb.conv
-                    rgb_base, rgb_s = self._rgb_base(tc), rgb_mods[i // 2]
-                # (events run out: later convolutions go unrecorded, not an IndexError)
-                ev = self.conv_events if (self.conv_events is not None
-                                          and self._conv_ev < len(self.conv_events)) else None
-                if ev is not None:
-                    ev[self._conv_ev][0].record()
-                x, part = conv3x3_f16x3_act(
-                    x, packed, cout, demod=demod_su, bias=sc.activate.bias,
-                    noise_weight=sc.noise.weight, noise=n,
-                    s_next=None if last else mods[i + 1], store_y=not last, rgb_base=rgb_base,
-                    rgb_s=rgb_s)
-                if ev is not None:
-                    ev[self._conv_ev][1].record()
-                    self._conv_ev += 1
-                    self.conv_flops += 2 * B * H * W * 9 * mc.weight.shape[2] * cout
-                if part is not None:
-                    rgb = rgb_finish(part, to_rgb.bias, skip=rgb if i else None, fir=self._fir)
-                continue
-            if (self.fuse_conv_t_blur and split[i] and mc.upsample and not last
-                    and split[i + 1] and i % 2 == 1 and conv_t_act_supported(x, cout)):
-                # upsampling conv with its blur and styled epilogue in the conv kernel
-                # (sdfr_conv_t_act: the same bits as the two launches below)
-                x = conv_t_act(x, packed, cout, fir=self._fir, demod=demod_su,
-                               bias=sc.activate.bias, noise_weight=sc.noise.weight,
-                               noise=noise[i], s_next=mods[i + 1])
-                continue
-            if split[i]:
-                out = conv3x3_f16x3(x, packed, cout, transposed=mc.upsample)
-                demod = demod_su              # result carries su (power of two): exact
-            else:
-                w = mc.scale * mc.weight[0]
-                demod = (torch.rsqrt((mods[i] * mods[i]) @ (w * w).sum([2, 3]).t() + 1e-8)
-                         if mc.demodulate else None)
-                if mc.upsample:
-                    out = F.conv_transpose2d(x, w.transpose(0, 1).contiguous(memory_format=cl),
-                                             stride=2)
-                else:
-                    out = F.conv2d(x, w.contiguous(memory_format=cl), padding=mc.padding)
-            if mc.upsample:
-                H, W = out.shape[2] - 1, out.shape[3] - 1
-            else:
-                H, W = out.shape[2], out.shape[3]
-            n = noise[i]
-            rgb_w = rgb_b = None
-            if i % 2 == 0:
-                to_rgb = self.to_rgb1 if i == 0 else self.to_rgbs[i // 2 - 1]
-                tc = to_rgb.conv
-                s_rgb = rgb_mods[i // 2]
-                rgb_w = self._rgb_base(tc)[None] * s_rgb[:, None, :]
-                rgb_b = to_rgb.bias
-            x, rgb_new = styled_epilogue(
-                out, fir=self._fir, bias=sc.activate.bias, noise_weight=sc.noise.weight,
-                noise=n, demod=demod, blur_up=mc.upsample,
-                s_next=None if last else mods[i + 1], store_y=not last,
-                rgb_w=rgb_w, rgb_b=rgb_b, skip=rgb if i else None,
-                split_y=not last and split[i + 1])
-            if rgb_new is not None:
-                rgb = rgb_new
-        return rgb
 
 
 _SIDE_STREAMS = {}
@@ -991,7 +607,9 @@ class Generator(nn.Module):
         self._dec_key = None
 
     def _decoder_weights_unchanged(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.decoder.parameters())
+        """Is the decoder's plan key the one of the last time this was asked?  (Asked right
+        after decoder.fused_ready(), which made the plan the current weights'.)"""
+        key = self.decoder._plan.key
         same = key == self._dec_key
         self._dec_key = key
         return same
@@ -1166,8 +784,8 @@ class Generator(nn.Module):
         feat_mod = None
         if (prepared is not None and self.fuse_feature_split
                 and B >= self.feature_split_min_batch
-                and self.decoder._conv_x(self.decoder.conv1.conv)):
-            feat_mod = prepared[2][0][0]
+                and self.decoder._plan.layers[0].split):
+            feat_mod = prepared.styles.mods[0]
         with torch.set_grad_enabled(grad_on):
             lat0 = latent[0][:, 0] if input_is_latent else latent[0]
             thumb_rgb, features, sdf, mask, xyz, eikonal_term = self.renderer(

@@ -275,7 +275,7 @@ class FullPipelineTrainer:
         d_ratio = t.d_reg_every / (t.d_reg_every + 1)
         # The reference builds one param group per decoder parameter, every one at the
         # same lr and betas (config.py:206-215).  Adam is elementwise, so a single group
-        # gives the same update bit for bit (test_train_step.py::test_g_adam_one_group_
+        # gives the same update bit for bit (tests/test_checkpoint.py::test_g_adam_one_group_
         # equals_per_parameter_groups) with ~6 foreach launches per step instead of ~6
         # per parameter.  checkpoint.load_into folds a per-group state into it.
         self.optimizer = torch.optim.Adam(self.g_train, lr=t.lr * g_ratio,

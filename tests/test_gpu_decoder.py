@@ -537,11 +537,19 @@ def test_decoder_fused_batch_chunks(sdfr):
     assert torch.equal(whole, torch.cat(halves, 0))
 
 
-@pytest.mark.parametrize("conv_impl,fuse", [("f16x3", True), ("f16x3", False), ("miopen", False)])
-def test_decoder_fused_equals_module_path(sdfr, conv_impl, fuse):
+@pytest.mark.parametrize("size,B,conv_impl,fuse", [
+    pytest.param(256, 2, "f16x3", True, id="f16x3-True"),
+    pytest.param(256, 2, "f16x3", False, id="f16x3-False"),
+    pytest.param(256, 2, "miopen", False, id="miopen-False"),
+    # 512^2: the 64-channel layers leave the split-fp16 path, so a split layer hands a
+    # channels_last activation to a MIOpen one (split_y off) and the last layer is MIOpen's
+    pytest.param(512, 1, "f16x3", True, id="512-f16x3-True"),
+])
+def test_decoder_fused_equals_module_path(sdfr, size, B, conv_impl, fuse):
     """Same weights, latents and noise: HIP-epilogue decoder == op-by-op decoder."""
     opt = sdfr.vol_render_opt()
     opt.model.feature_encoder_in_channels = opt.rendering.width   # as Generator.__init__ sets it
+    opt.model.size = size
     torch.manual_seed(0)
     dec = sdfr.Decoder(opt.model).to(DEV).eval()
     dec.conv_impl = conv_impl
@@ -552,22 +560,131 @@ def test_decoder_fused_equals_module_path(sdfr, conv_impl, fuse):
                 m.weight.fill_(0.1)
             if isinstance(m, sdfr.FusedLeakyReLU):
                 m.bias.normal_(0, 0.1)
-    B = 2
     feats = torch.randn(B, 256, 64, 64, device=DEV)
     z = [torch.randn(B, 256, device=DEV)]
-    noise = [torch.randn(B, 1, 2 ** r, 2 ** r, device=DEV) for r in (6, 7, 7, 8, 8)]
+    res = (6, 7, 7, 8, 8) if size == 256 else (6, 7, 7, 8, 8, 9, 9)
+    noise = [torch.randn(B, 1, 2 ** r, 2 ** r, device=DEV) for r in res]
     with torch.no_grad():
         assert dec._fused_ok(feats, None, None)
         fused, _ = dec(feats, z, noise=noise)
         dec.use_fused = False
         mod, _ = dec(feats, z, noise=noise)
         dec.use_fused = True
-    assert fused.shape == mod.shape == (B, 3, 256, 256)
+    assert fused.shape == mod.shape == (B, 3, size, size)
     scale = float(mod.abs().max())
-    tag = conv_impl + ("_act" if fuse else "")
+    tag = conv_impl + ("_act" if fuse else "") + ("" if size == 256 else f"_{size}")
     _record[f"decoder_fused_vs_module_scale_{tag}"] = scale
     _close(f"decoder_fused_vs_module_{tag}", fused.cpu(), mod.cpu(), 1e-4 * max(1.0, scale),
            1e-5 * max(1.0, scale))
+
+
+@pytest.fixture(scope="module")
+def default_decoder(sdfr):
+    opt = sdfr.vol_render_opt()
+    opt.model.feature_encoder_in_channels = opt.rendering.width
+    torch.manual_seed(0)
+    return sdfr.Decoder(opt.model).to(DEV).eval()
+
+
+# rsqrtf's error, relative, in units of 2^-24.  The ROCm math documentation (the HIP math API
+# page, which tabulates each device function's error) was not at hand when this test was
+# written -- the ROCm installation ships no copy of it -- so the figure is a measured one: the
+# worst relative error of the demodulations against float64 over the cases below was
+# MEASURED_DEMOD x 2^-24 on an MI355X (sum and rsqrtf together; 1.88 / 2.11 / 2.29 at B = 1 /
+# 17 / 1027), and twice that stands in for rsqrtf's share.
+MEASURED_DEMOD = 2.29
+RSQRTF_REL = 2 * MEASURED_DEMOD
+
+
+@pytest.mark.parametrize("conv_impl", ["f16x3", "miopen"])
+@pytest.mark.parametrize("B", [1, 17, 1027])
+def test_decoder_styles_vs_fp64(default_decoder, B, conv_impl):
+    """sdfr_decoder_styles through the plan's own argument filling, on the default decoder:
+    B = 1 (one partial 16-row block), 17 (a second partial block) and 1027 (65 blocks: the
+    grid-stride loop wraps past its 64); f16x3 demodulates 5 layers, miopen none.
+
+    Modulations against float64 on the stacked weights: |err| <= d 2^-24 (sum |x w scale|
+    + |b lr_mul|) with d = 15, the roundings on style_mod_kernel's longest summation path
+    for K = 512: K / 64 = 8 fmas per lane, 6 butterfly adds, 1 bias add.
+
+    Demodulations against float64 rsqrt(eps + m^2 . wsq) of the kernel's own fp32
+    modulations: the sum has 16 roundings (1 squaring, cmax / 64 = 8 fmas, 6 butterfly adds,
+    1 eps add) and only positive terms, so its relative error is <= 16 x 2^-24, of which the
+    square root keeps half; plus rsqrtf's own (RSQRTF_REL)."""
+    dec = default_decoder
+    dec.conv_impl = conv_impl
+    try:
+        plan = dec._fused_plan().load()
+        g = torch.Generator(device=DEV).manual_seed(B)
+        latent = torch.randn(B, dec.n_latent, 512, device=DEV, generator=g)
+        sty = plan.styles(latent)
+        torch.cuda.synchronize()
+        u = 2.0 ** -24
+        assert plan.K == 512 and plan.cmax == 512
+        worst = 0.0
+        for k, got in enumerate(list(sty.mods) + list(sty.rgb_mods)):
+            c = plan.mod_c[k]
+            x = latent[:, plan.mod_index[k]].double()
+            lin = plan.lins[k]
+            with torch.no_grad():             # the stack is the module's own fp32 products
+                assert torch.equal(plan.mod_w[k, :c], lin.weight * lin.scale)
+                assert torch.equal(plan.mod_b[k, :c], lin.bias * lin.lr_mul)
+            w, b = plan.mod_w[k, :c].double(), plan.mod_b[k, :c].double()
+            bound = 15 * u * (x.abs() @ w.abs().t() + b.abs())
+            ratio = float(((got.double() - (x @ w.t() + b)).abs() / bound).max())
+            worst = max(worst, ratio)
+            assert got.shape == (B, c) and ratio <= 1.0, (k, ratio)
+        _record[f"styles_mod_B{B}_{conv_impl}_over_bound"] = worst
+        assert sorted(sty.demods) == ([0, 1, 2, 3, 4] if conv_impl == "f16x3" else [])
+        worst = 0.0
+        for j, (i, got) in enumerate(sorted(sty.demods.items())):
+            ly = plan.layers[i]
+            # the stacked sums against the module's weight in float64: su^2 sum (scale w)^2
+            # with su a power of two (exact); the fp32 stack rounds scale to fp32 and the
+            # product scale * w (each counted twice in the square), the square and 8 adds
+            # of positive terms: <= 13 x 2^-24 relative
+            mc, su = ly.sc.conv, ly.su.double()
+            assert torch.all(ly.su == torch.exp2(torch.round(torch.log2(ly.su))))
+            w64 = mc.weight[0].detach().double() * mc.scale
+            wsq = (w64 * w64).sum([2, 3]) * (su * su)[:, None]
+            stack = plan.dem_w[j].double()
+            assert float(((stack[:ly.cout, :ly.cin] - wsq).abs() / wsq).max()) <= 13 * u
+            assert not stack[ly.cout:].any() and not stack[:, ly.cin:].any()
+            assert torch.equal(plan.dem_eps[j, :ly.cout].double(),
+                               su * su * torch.tensor(1e-8, dtype=torch.float32).double())
+            assert not plan.dem_eps[j, ly.cout:].any()
+            m = sty.mods[i].double()
+            ref = torch.rsqrt(plan.dem_eps[j, :ly.cout].double()
+                              + (m * m) @ plan.dem_w[j, :ly.cout, :ly.cin].double().t())
+            rel = float(((got.double() - ref).abs() / ref).max()) / u
+            worst = max(worst, rel)
+            print(f"demod layer {i} B {B}: worst relative error {rel:.3f} x 2^-24")
+            assert got.shape == (B, ly.cout)
+        _record[f"styles_demod_B{B}_{conv_impl}_rel_2p-24"] = worst
+        assert worst <= 8 + RSQRTF_REL, worst
+    finally:
+        dec.conv_impl = "f16x3"
+
+
+def test_decoder_unsupported_latent_width_runs_module_path(sdfr):
+    """A decoder whose latent width (style_dim 64 -> 128) sdfr_decoder_styles does not take
+    is not fused_ready: forward() runs the module path, bit for bit use_fused = False."""
+    opt = sdfr.vol_render_opt()
+    opt.model.feature_encoder_in_channels = opt.rendering.width
+    opt.model.style_dim = 64
+    torch.manual_seed(0)
+    dec = sdfr.Decoder(opt.model).to(DEV).eval()
+    feats = torch.randn(2, 256, 64, 64, device=DEV)
+    z = [torch.randn(2, 64, device=DEV)]
+    outs = []
+    with torch.no_grad():
+        assert not dec.fused_ready(torch.device(DEV)) and not dec._fused_ok(feats, None, None)
+        for fused in (True, False):
+            dec.use_fused = fused
+            torch.manual_seed(5)                  # the module path draws its noise per layer
+            outs.append(dec(feats, z)[0])
+    assert outs[0].shape == (2, 3, 256, 256)
+    assert torch.equal(outs[0], outs[1])
 
 
 def test_decoder_conv_t_blur_fusion_bit_exact(sdfr):
