@@ -1129,6 +1129,79 @@ int sdfr_mesh_cc_select_emit(const float *verts, const int32_t *faces, uint32_t 
                              void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Mesh simplification (added to ABI 15 without a version step: additive;
+ * csrc/mesh_simplify.hip): vertex clustering on a uniform grid -- where users of the
+ * reference decimate with trimesh on the host.  All vertices of one grid cell become one
+ * vertex at their (quantised) mean; faces are remapped, collapsed ones dropped, duplicates
+ * removed.  Every output is a pure function of the mesh and the grid (integer atomics only),
+ * so a NumPy transcription (tests/mesh_simplify_ref.py) gives the same bits.
+ *
+ * Inputs.  verts [V,3] fp32 and faces [F,3] int32 on the device, 1 <= V < 2^31,
+ * 3 F < 2^31, F may be 0.  Grid: origin (ox, oy, oz) fp32 (finite), cell edge `cell` fp32
+ * (finite, > 0), nx, ny, nz each in [1, 2^21] (a cell key fits 63 bits).  Every
+ * floating-point step below is one rounded IEEE operation (round to nearest even, nothing
+ * contracted).
+ *
+ * Cell of a vertex, per axis k:  t_k = (v_k - o_k) / cell (one fp32 subtract, one correctly
+ * rounded fp32 divide);  c_k = clamp(floor(t_k), 0, n_k - 1), clamped as float before the
+ * conversion, so a vertex outside the grid belongs to the nearest boundary cell;
+ * key = (c_x ny + c_y) nz + c_z in 64 bits.  A non-finite coordinate is an error.
+ *
+ * Clusters.  A cluster is the set of vertices with one key; every vertex takes part,
+ * referenced by a face or not.  rep = the cluster's smallest vertex index; clusters are
+ * numbered 0..C-1 in increasing order of rep.
+ *
+ * Position of a cluster, per axis:  r_k = clamp(t_k - (float)c_k, 0, 1) in fp32;
+ * q_k = (int64) rint(r_k 2^20) (the product is exact);  S_k = sum of q_k over the members
+ * in int64 (< 2^52 for any V), m = the member count;
+ *   p_k = (float)( (double)o_k + ((double)c_k + (double)S_k / ((double)m 2^20)) (double)cell )
+ * with each fp64 operation rounded once and c_k the cell of rep.
+ *
+ * Faces.  Each corner is mapped to its cluster.  A face with two equal corners is dropped.
+ * Two surviving faces with the same vertex SET (any corner order, either orientation) are
+ * duplicates: of a class of duplicates the face with the smallest original index is kept,
+ * with its own corner order.  Kept faces keep their original relative order.
+ *
+ * Vertices out.  With drop_unreferenced != 0 a cluster that no kept face references is
+ * dropped, otherwise all C are kept; kept clusters are renumbered densely in the same order.
+ *
+ * Not promised: manifoldness (clustering can pinch a thin part into a non-manifold edge or
+ * vertex) and feature preservation (the mean pulls a convex surface inwards, by less than
+ * one cell).  Guaranteed for vertices inside the grid: a vertex and its cluster's position
+ * lie in one cell, so they differ by at most `cell` per axis.
+ *
+ *   sdfr_mesh_simplify_count: everything up to the scans, into ws; counts [3] in HOST
+ *                       memory = C, V_out, F_out (synchronises stream).
+ *   sdfr_mesh_simplify_emit:  same mesh and ws (after the count; the grid is kept in ws),
+ *                       V_out / F_out the counts: verts_out [V_out,3], faces_out [F_out,3]
+ *                       int32, index_map [V_out] int32 (new vertex -> rep, an old vertex: the
+ *                       map that carries attributes), cluster [V] int32 (old vertex -> new
+ *                       vertex, or -1 when its cluster was dropped; may be null), members
+ *                       [V_out] uint32 (may be null).
+ *
+ * ws: sdfr_mesh_simplify_workspace_bytes(V, F) bytes, a function of V and F only (two
+ * hash tables of the powers of two >= 2 V and >= 2 F slots of 12 and 4 bytes, 44 bytes per
+ * vertex, 8 per face, the scans' block sums; 0 for sizes outside the limits).
+ * SDFR_EINVAL before any launch, nothing written, for null pointers (faces may be null
+ * when F is 0; cluster and members may be null), V or F outside the limits, cell not finite
+ * or <= 0, a non-finite origin, a dimension outside [1, 2^21], a short workspace, V_out
+ * outside [1, V] or F_out > F.  A face index outside [0, V) or a non-finite vertex
+ * coordinate is never used to address memory: the kernels skip the element and set a device
+ * error word, which the count call reads with its counts and returns as SDFR_EINVAL
+ * ("... outside [0, V)" / "... not finite"; counts unwritten).  Everything but that read is
+ * asynchronous on stream; nothing allocates.
+ * ------------------------------------------------------------------------- */
+size_t sdfr_mesh_simplify_workspace_bytes(uint32_t V, uint32_t F);
+int sdfr_mesh_simplify_count(const float *verts, const int32_t *faces, uint32_t V, uint32_t F,
+                             float ox, float oy, float oz, float cell,
+                             uint32_t nx, uint32_t ny, uint32_t nz, int drop_unreferenced,
+                             void *ws, size_t ws_bytes, uint32_t *counts, void *stream);
+int sdfr_mesh_simplify_emit(const float *verts, const int32_t *faces, uint32_t V, uint32_t F,
+                            uint32_t V_out, uint32_t F_out, const void *ws, size_t ws_bytes,
+                            float *verts_out, int32_t *faces_out, int32_t *index_map,
+                            int32_t *cluster, uint32_t *members, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Mesh rasteriser (added to ABI 15 without a version step: additive; csrc/raster.hip):
  * B views of one indexed mesh with the render's own pinhole camera, the nearest triangle
  * per pixel, deterministic.  Where the reference rasterises with pytorch3d

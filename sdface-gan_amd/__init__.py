@@ -28,6 +28,9 @@ generic driver), SparseVolume, cube_axis; mesh_components -> Components / keep_c
 (a mesh's connected components labelled, measured, filtered and compacted on the GPU:
 csrc/mesh_cc.hip, sdfr_mesh_cc_*; label_components, component_stats, sparse_mesh the pieces;
 extract_mesh_sparse(components={"largest": 1}) filters before the host copy);
+simplify_mesh -> Simplified (vertex clustering on a uniform grid, reproducible bit for bit:
+csrc/mesh_simplify.hip, sdfr_mesh_simplify_*; simplify_grid its default grid;
+extract_mesh_sparse(simplify=k) thins the mesh before the host copy);
 rasterize_mesh -> Raster (B views of a Mesh, nearest
 triangle per pixel with depth and perspective-correct barycentrics, deterministic:
 csrc/raster.hip, sdfr_mesh_raster), interpolate_vertex_attributes (sdfr_mesh_interpolate),
@@ -45,11 +48,13 @@ from .generator import (Blur, Decoder, EqualLinear, FusedLeakyReLU, Generator,  
                         MappingLinear, ModulatedConv2d, NoiseInjection, PixelNorm, StyledConv,
                         ToRGB, Upsample, fused_leaky_relu, make_kernel, upfirdn2d)
 from .graphs import GraphedGenerator  # noqa: F401
-from .mesh import (Components, Mesh, SparseVolume, align_volume, color_mesh,  # noqa: F401
+from .mesh import (Components, Mesh, Simplified, SparseVolume, align_volume,  # noqa: F401
+                   color_mesh,
                    component_stats, cube_axis, cube_points, eikonal_residual,
                    extract_mesh_sparse, extract_mesh_with_marching_cubes, keep_components,
                    label_components, marching_cubes, mesh_components, normal_mesh, sdf_cube,
-                   shade_surface, sparse_extract, sparse_mesh, world_to_network, xyz2mesh)
+                   shade_surface, simplify_grid, simplify_mesh, sparse_extract, sparse_mesh,
+                   world_to_network, xyz2mesh)
 from .raster import (Raster, interpolate_vertex_attributes, load_obj, rasterize_mesh,  # noqa: F401
                      render_mesh, subdivide_mesh)
 from .options import AttrDict, SDFOptions, vol_render_opt  # noqa: F401

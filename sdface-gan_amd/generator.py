@@ -679,7 +679,9 @@ class Generator(nn.Module):
         """The mesh of the face of ``styles`` (one face) from narrow-band bricks: the
         mapping network and truncation of ``query_field``, then ``mesh.extract_mesh_sparse``
         (``kw``: level, lipschitz, grow, return_volume, components -- e.g.
-        ``components={"largest": 1}`` keeps the largest connected component) -> ``Mesh``."""
+        ``components={"largest": 1}`` keeps the largest connected component -- and simplify:
+        ``simplify=4`` clusters the vertices of 4^3 lattice cells on the GPU before the copy)
+        -> ``Mesh``."""
         from .mesh import extract_mesh_sparse
         lat0 = self._renderer_latent(styles, truncation, truncation_latent, input_is_latent)
         return extract_mesh_sparse(self.renderer, lat0, res=res, **kw)

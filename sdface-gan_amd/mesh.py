@@ -530,16 +530,171 @@ def keep_components(mesh_or_verts, faces=None, *, keep=None, largest=None, min_f
                 None if mesh.vertex_normals is None else mesh.vertex_normals[im])
 
 
+Simplified = namedtuple("Simplified", ("verts", "faces", "index_map", "cluster", "members"))
+Simplified.__doc__ = """A mesh simplified by vertex clustering (``simplify_mesh``), on the GPU:
+``verts`` [V', 3] fp32, ``faces`` [F', 3] int32, ``index_map`` [V'] int32 (new vertex -> the
+smallest old vertex of its cluster: the map that carries attributes), ``cluster`` [V] int32 (old
+vertex -> new vertex, or -1 when its cluster was dropped) and ``members`` [V'] int32 (vertices
+merged into each new one)."""
+
+_MAX_SIMPLIFY_DIM = 2 ** 21
+
+
+def simplify_grid(lo, hi, cell=None, cells=None):
+    """The default grid of ``simplify_mesh`` for a bounding box ``lo`` .. ``hi`` (three numbers
+    each): ``(origin, cell, dims)``.  The origin is ``lo``; ``cell`` is the given edge length,
+    or with ``cells`` the longest edge of the box divided by ``cells``, rounded to fp32;
+    ``dims[k] = floor((hi[k] - lo[k]) / cell) + 1`` (in Python floats, from that fp32 cell).
+    ValueError unless exactly one of ``cell`` / ``cells`` is given, for a box or cell that is
+    not finite, a cell that is not positive, or a grid finer than 2^21 cells along an axis."""
+    if (cell is None) == (cells is None):
+        raise ValueError("simplify_mesh: give exactly one of cell (the edge length) and cells "
+                         "(the number of cells along the longest edge of the bounding box)")
+    lo, hi = [float(x) for x in lo], [float(x) for x in hi]
+    if len(lo) != 3 or len(hi) != 3 or not np.isfinite(lo + hi).all():
+        raise ValueError("simplify_mesh: a vertex coordinate is not finite")
+    extent = [h - l for l, h in zip(lo, hi)]
+    if cells is not None:
+        if not np.isfinite(cells) or cells <= 0:
+            raise ValueError(f"simplify_mesh: cells must be a positive number, not {cells!r}")
+        cell = max(extent) / float(cells)
+    cell = float(np.float32(cell)) if np.isfinite(cell) else float("nan")
+    if not np.isfinite(cell) or cell <= 0:
+        raise ValueError(f"simplify_mesh: the cell edge must be finite and > 0, not {cell!r}"
+                         + (" (the bounding box has no extent)" if cells is not None else ""))
+    dims = tuple(int(e / cell) + 1 for e in extent)          # (e >= 0: int() is floor)
+    _check_simplify_dims(dims)
+    return tuple(lo), cell, dims
+
+
+def _check_simplify_dims(dims):
+    if len(dims) != 3 or any(int(d) != d or not 1 <= d <= _MAX_SIMPLIFY_DIM for d in dims):
+        raise ValueError(f"simplify_mesh: dims must be three integers in [1, 2^21], got {dims} "
+                         "(a finer grid needs a larger cell)")
+
+
+def _simplify_check(rc: int, what: str):
+    """``_lib.check``, with the device-side findings as ValueError."""
+    from . import _lib
+    if rc == _lib.SDFR_EINVAL:
+        msg = _lib.lib().sdfr_last_error().decode(errors="replace")
+        if "outside [0," in msg or "not finite" in msg:
+            raise ValueError(f"{what}: {msg}")
+    _lib.check(rc, what)
+
+
+def simplify_mesh(mesh_or_verts, faces=None, *, cell=None, cells=None, origin=None, dims=None,
+                  drop_unreferenced=True):
+    """The mesh simplified by vertex clustering on a uniform grid, on the GPU
+    (csrc/mesh_simplify.hip, ``sdfr_mesh_simplify_count`` / ``_emit``; include/sdfr.h, "Mesh
+    simplification") -- where users of the reference decimate with trimesh on the host.  All
+    vertices of one grid cell become one vertex at their mean (quantised to 2^-20 of the cell,
+    so the result is reproducible bit for bit); a face whose corners no longer differ is
+    dropped, and of faces with the same three vertices the first is kept.
+
+    Exactly one of ``cell`` (the cell's edge length) and ``cells`` (the number of cells along
+    the longest edge of the bounding box).  ``origin`` (three numbers) and ``dims`` (three
+    integers in [1, 2^21]) fix the grid; without them the origin is the bounding box's minimum
+    and ``dims[k] = floor(extent[k] / cell) + 1`` (``simplify_grid``).  A vertex outside the
+    grid belongs to the nearest boundary cell.  ``drop_unreferenced`` drops the new vertices
+    that no kept face references.
+
+    A ``Mesh`` (host arrays) gives a new ``Mesh``; its ``vertex_colors`` / ``vertex_normals``
+    are those of each cluster's representative (``[index_map]``) -- call ``color_mesh`` /
+    ``normal_mesh`` again for the field's exact values at the new vertices.  ``verts`` [V, 3]
+    fp32 and ``faces`` [F, 3] int32 | int64 on the GPU give a ``Simplified`` named tuple, all
+    on the GPU.
+
+    Not promised: manifoldness (clustering can pinch thin parts) and feature preservation (the
+    mean pulls a convex surface inwards, by less than one cell).  Guaranteed for vertices
+    inside the grid: a vertex and the new vertex of its cluster lie in one cell.
+
+    ValueError for bad selectors, a face index outside [0, V), a non-finite coordinate, or
+    when no face survives with ``drop_unreferenced`` (the cell is too coarse for the mesh).
+    There is no CPU path."""
+    from . import _lib
+    what = "simplify_mesh"
+    if (cell is None) == (cells is None):
+        raise ValueError("simplify_mesh: give exactly one of cell (the edge length) and cells "
+                         "(the number of cells along the longest edge of the bounding box)")
+    if cell is not None and not (np.isfinite(cell) and cell > 0):
+        raise ValueError(f"simplify_mesh: the cell edge must be finite and > 0, not {cell!r}")
+    if cells is not None and not (np.isfinite(cells) and cells > 0):
+        raise ValueError(f"simplify_mesh: cells must be a positive number, not {cells!r}")
+    if origin is not None:
+        origin = tuple(float(x) for x in origin)
+        if len(origin) != 3 or not np.isfinite(origin).all():
+            raise ValueError(f"simplify_mesh: origin must be three finite numbers, got {origin}")
+    if dims is not None:
+        dims = tuple(dims)
+        _check_simplify_dims(dims)
+    verts, faces, mesh = _cc_inputs(what, mesh_or_verts, faces)
+    if origin is None or dims is None or cells is not None:
+        lo, hi = (t.cpu().tolist() for t in verts.aminmax(dim=0))
+        _, cell, box_dims = simplify_grid(lo, hi, cell, cells)
+        if origin is None:
+            origin = tuple(lo)
+        elif dims is None:                           # the box as seen from the given origin
+            box_dims = simplify_grid(origin, [max(h, o) for h, o in zip(hi, origin)],
+                                     cell=cell)[2]
+        dims = box_dims if dims is None else dims
+    L = _lib.lib()
+    st = _lib.stream_of(verts)
+    dev = verts.device
+    V, F = verts.shape[0], faces.shape[0]
+    n = L.sdfr_mesh_simplify_workspace_bytes(V, F)
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    counts = (_lib._u32 * 3)()
+    _simplify_check(L.sdfr_mesh_simplify_count(
+        _lib.ptr(verts), _lib.ptr(faces), V, F, origin[0], origin[1], origin[2], float(cell),
+        int(dims[0]), int(dims[1]), int(dims[2]), int(bool(drop_unreferenced)), _lib.ptr(ws), n,
+        counts, st), what)
+    nv, nf = int(counts[1]), int(counts[2])
+    if nv == 0:
+        raise ValueError("simplify_mesh: no face survives: the cell is too coarse for this mesh "
+                         f"({int(counts[0])} clusters; pass drop_unreferenced=False to get them)")
+    out_v = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    index_map = torch.empty(nv, dtype=torch.int32, device=dev)
+    cluster = torch.empty(V, dtype=torch.int32, device=dev)
+    members = torch.empty(nv, dtype=torch.int32, device=dev)
+    _simplify_check(L.sdfr_mesh_simplify_emit(
+        _lib.ptr(verts), _lib.ptr(faces), V, F, nv, nf, _lib.ptr(ws), n, _lib.ptr(out_v),
+        _lib.ptr(out_f), _lib.ptr(index_map), _lib.ptr(cluster), _lib.ptr(members), st), what)
+    if mesh is None:
+        return Simplified(out_v, out_f, index_map, cluster, members)
+    im = index_map.cpu().numpy()
+    return Mesh(out_v.cpu().numpy(), out_f.cpu().numpy(),
+                None if mesh.vertex_colors is None else mesh.vertex_colors[im],
+                None if mesh.vertex_normals is None else mesh.vertex_normals[im])
+
+
+def _check_simplify_factor(simplify, what):
+    if simplify is None:
+        return None
+    if isinstance(simplify, bool) or int(simplify) != simplify or simplify < 2:
+        raise ValueError(f"{what}: simplify must be None or an integer >= 2 (lattice cells per "
+                         f"cluster cell), not {simplify!r}")
+    return int(simplify)
+
+
 def sparse_mesh(evaluate, axes, res: int, seeds: torch.Tensor, level: float = 0.0,
-                grow: bool = True, components=None):
+                grow: bool = True, components=None, simplify=None):
     """``sparse_extract`` and ``extract_mesh_sparse``'s finish: ``(Mesh, SparseVolume)`` with
     the vertices scaled to (v / res - 0.5) * 0.24 per axis and y, z negated, on the host.
     ``components``: ``None``, or a dict of ``keep_components`` keyword arguments that filters
     the mesh on the GPU before the scaling and before the copy to the host (so only what is
-    kept is copied)."""
+    kept is copied).  ``simplify``: ``None``, or an integer k >= 2: after that filter (a floater
+    is never merged into the face) and before the scaling and the copy, ``simplify_mesh`` in
+    index coordinates on the grid of origin 0, cell k and ceil(res / k) cells per axis -- a
+    function of ``res`` and k alone, not of the mesh."""
+    simplify = _check_simplify_factor(simplify, "sparse_mesh")
     verts, faces, volume = sparse_extract(evaluate, axes, res, seeds, level, grow)
     if components is not None:
         verts, faces, _ = keep_components(verts, faces, **components)
+    if simplify is not None:
+        verts, faces = simplify_mesh(verts, faces, cell=float(simplify), origin=(0.0, 0.0, 0.0),
+                                     dims=(-(-res // simplify),) * 3)[:2]
     for axis in range(3):
         verts[:, axis] = (verts[:, axis] / float(res) - 0.5) * 0.24
     verts[:, 2] *= -1
@@ -549,7 +704,7 @@ def sparse_mesh(evaluate, axes, res: int, seeds: torch.Tensor, level: float = 0.
 
 def extract_mesh_sparse(renderer, styles: torch.Tensor, res: int = 512, level: float = 0.0,
                         lipschitz=None, grow: bool = True, return_volume: bool = False,
-                        components=None):
+                        components=None, simplify=None):
     """The ``level`` set of the field itself at ``res``^3 without the dense cube: the
     ``Mesh`` that ``extract_mesh_with_marching_cubes(sdf_cube(renderer, styles, res))``
     gives (same vertex scaling and y / z flips, the same triangles with bit-equal
@@ -573,9 +728,16 @@ def extract_mesh_sparse(renderer, styles: torch.Tensor, res: int = 512, level: f
     arguments, e.g. ``{"largest": 1}``: the mesh is split into its connected components and
     filtered on the GPU before the vertex scaling and before the copy to the host, so the
     unwanted components are never copied.  The components' bounding boxes and areas then
-    refer to index coordinates (0 .. res - 1 per axis), not to world coordinates."""
+    refer to index coordinates (0 .. res - 1 per axis), not to world coordinates.
+
+    ``simplify``: ``None`` (the mesh as extracted), or an integer k >= 2: the mesh is thinned by
+    vertex clustering (``simplify_mesh``) with k lattice cells per cluster cell, on the GPU,
+    after the ``components`` filter and before the vertex scaling and the copy to the host --
+    about 1 / k^2 of the vertices and faces are copied.  The grid depends on ``res`` and k
+    only.  Not promised: manifoldness and sharp features (see ``simplify_mesh``)."""
     if styles.shape[0] != 1:
         raise ValueError("extract_mesh_sparse: one mesh, one face (styles [1, 256])")
+    simplify = _check_simplify_factor(simplify, "extract_mesh_sparse")
     nb = _check_brick_res(res, "extract_mesh_sparse")
     if not styles.is_cuda:
         raise RuntimeError("extract_mesh_sparse: needs the GPU (HIP kernels)")
@@ -596,7 +758,8 @@ def extract_mesh_sparse(renderer, styles: torch.Tensor, res: int = 512, level: f
                               .norm(dim=-1).max())
         band = float(lipschitz) * 4.0 * (3.0 ** 0.5) * (2.0 / res)
         seeds = (sdf_c.reshape(-1).float() - level).abs() <= band
-        mesh, volume = sparse_mesh(evaluate, axes, res, seeds, level, grow, components)
+        mesh, volume = sparse_mesh(evaluate, axes, res, seeds, level, grow, components,
+                                   simplify)
     return (mesh, volume) if return_volume else mesh
 
 
