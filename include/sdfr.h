@@ -1202,6 +1202,92 @@ int sdfr_mesh_simplify_emit(const float *verts, const int32_t *faces, uint32_t V
                             int32_t *cluster, uint32_t *members, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Mesh smoothing (added to ABI 15 without a version step: additive;
+ * csrc/mesh_smooth.hip): Laplacian and Taubin lambda | mu passes of the uniform umbrella
+ * operator on an indexed triangle mesh -- where users of the reference call trimesh's
+ * filter_laplacian / filter_taubin on the host.  Floating-point sums over a vertex's
+ * neighbours would depend on their order, so the state of the smoothing is integer: every
+ * output is a pure function of the mesh, the lattice and the weights, and a NumPy
+ * transcription (tests/mesh_smooth_ref.py) gives the same bits.
+ *
+ * Inputs.  verts [V,3] fp32 and faces [F,3] int32 on the device, 1 <= V < 2^31,
+ * 3 F < 2^31, F may be 0.
+ *
+ * Lattice.  Origin (ox, oy, oz) fp32 (finite) and unit_log2 in [-126, 96]: the unit
+ * u = 2^unit_log2 is a normal fp32 and 2^31 u is finite in fp32.  Per vertex and axis
+ * q = (int64) rint(((double)v - (double)o) / u): one fp64 subtraction, an exact scaling,
+ * ties to even.  Every input q must lie in [0, 2^30]; a vertex outside the lattice or a
+ * non-finite coordinate is an error, not clamped.
+ *
+ * Valence.  d_i = the number of face corners equal to i (a face that lists i twice counts
+ * twice).
+ *
+ * Boundary.  The edge slots of a face (c0, c1, c2) are {c0,c1}, {c1,c2}, {c2,c0}; slots with
+ * equal ends are ignored.  The multiplicity of an unordered pair is the number of slots, over
+ * all faces, that equal it.  A vertex is a boundary vertex when it is an end of a pair of
+ * multiplicity exactly 1 (non-manifold pairs, 3 and more, do not make a boundary).
+ *
+ * Movable.  d_i > 0 and not (pin_boundary and boundary).
+ *
+ * One pass of weight w = (double)weight_p (fp32, finite, |w| <= 1), a Jacobi pass: every read
+ * is from the previous pass's state.  For every movable i and every axis:
+ *   S = the sum, over the corners equal to i, of q[a] + q[b], a and b that face's other two
+ *       corners as written (int64, exact);
+ *   D = S - 2 d_i q[i] (exact);
+ *   q'[i] = clamp(q[i] + (int64) rint((w (double)D) / (double)(2 d_i)), -2^30, 2^31 - 1)
+ * -- one fp64 conversion, one product, one quotient, rint with ties to even.  The clamp is a
+ * guard that never acts on a sane mesh (one bounding-box extent of slack on either side); it
+ * keeps the state in int32, and with it |S| <= 2 d_i (2^31 - 1) and |D| < 3 d_i 2^31: S fits
+ * int64 for every permitted mesh (d_i <= 3 F < 2^31), D for d_i <= 2^30.  A vertex with more
+ * than 2^30 corners (over 4 GiB of faces on one vertex) is outside the definition.  On a
+ * closed manifold this is the uniform umbrella operator (each neighbour is counted twice).
+ *
+ * Output.  A vertex that was never movable keeps its input coordinates bit for bit, and so
+ * does every vertex after 0 passes.  Every other vertex:
+ *   p = (float)((double)o + (double)q u)
+ * (the product is exact; one fp64 sum, one rounding to fp32).  Faces are not touched.
+ *
+ * Schedule.  The run call takes a plain array of weights: Laplacian with n iterations is n
+ * passes of weight lambda, Taubin n times (lambda, mu), 2 n passes.
+ *
+ *   sdfr_mesh_smooth_prepare: what all passes share, into ws (the quantised state, every
+ *                       vertex's row of neighbours, the movable flags, the lattice); valence
+ *                       [V] int32 and boundary [V] uint8 (0 / 1) are device outputs, either
+ *                       may be null.  Reads the device error word (synchronises stream).
+ *   sdfr_mesh_smooth_run:     same verts, V and ws (after a prepare that returned SDFR_OK);
+ *                       weights [n_passes] fp32 in HOST memory, 0 <= n_passes <= 1024 (null
+ *                       allowed when 0); verts_out [V,3] fp32, which must not overlap verts.
+ *                       Asynchronous on stream.  May be called repeatedly after one prepare:
+ *                       each call starts from the prepared state.
+ *
+ * ws: sdfr_mesh_smooth_workspace_bytes(V, F) bytes, a function of V and F only.  With
+ * up(x) = x rounded up to a multiple of 256, Ce = the power of two >= max(4 F, 1) and
+ * nb = ceil(V / 2048):
+ *   up(4 (V + 1)) + up(4 V) + up(V) + 256 + 3 up(16 V) + up(4 nb + 4) + up(24 F) + up(4 Ce)
+ *   + up(8 Ce)
+ * (57 bytes per vertex, 24 per face, 12 per edge-table slot; 0 for sizes outside the limits).
+ * Both calls return SDFR_EINVAL before any launch, nothing written, for null pointers (faces
+ * may be null when F is 0), V or F outside the limits, a short workspace, a non-finite
+ * origin, unit_log2 outside [-126, 96], a weight that is not finite or has |w| > 1,
+ * n_passes > 1024, or verts_out overlapping verts.  run is not given F: what it reads is laid
+ * out at offsets that depend on V alone, the rows after the rest, and it rejects a workspace
+ * shorter than sdfr_mesh_smooth_workspace_bytes(V, 0); with a ws_bytes between that and the
+ * size prepare was given, no row beyond ws_bytes is read (such a vertex does not move).  A face index outside [0, V), a non-finite
+ * vertex coordinate or a vertex outside the lattice is never used to address memory: the
+ * kernels skip the element and set a device error word, which prepare reads and returns as
+ * SDFR_EINVAL ("... outside [0, V)" / "... not finite" / "... outside the lattice").
+ * Everything but that read is asynchronous on stream; nothing allocates.
+ * ------------------------------------------------------------------------- */
+size_t sdfr_mesh_smooth_workspace_bytes(uint32_t V, uint32_t F);
+int sdfr_mesh_smooth_prepare(const float *verts, const int32_t *faces, uint32_t V, uint32_t F,
+                             float ox, float oy, float oz, int unit_log2, int pin_boundary,
+                             void *ws, size_t ws_bytes, int32_t *valence, uint8_t *boundary,
+                             void *stream);
+int sdfr_mesh_smooth_run(const float *verts, uint32_t V, const float *weights,
+                         uint32_t n_passes, const void *ws, size_t ws_bytes, float *verts_out,
+                         void *stream);
+
+/* ---------------------------------------------------------------------------
  * Mesh rasteriser (added to ABI 15 without a version step: additive; csrc/raster.hip):
  * B views of one indexed mesh with the render's own pinhole camera, the nearest triangle
  * per pixel, deterministic.  Where the reference rasterises with pytorch3d

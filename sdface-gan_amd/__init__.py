@@ -31,6 +31,10 @@ extract_mesh_sparse(components={"largest": 1}) filters before the host copy);
 simplify_mesh -> Simplified (vertex clustering on a uniform grid, reproducible bit for bit:
 csrc/mesh_simplify.hip, sdfr_mesh_simplify_*; simplify_grid its default grid;
 extract_mesh_sparse(simplify=k) thins the mesh before the host copy);
+smooth_mesh -> Smoothed (Laplacian / Taubin passes on an integer lattice, reproducible bit for
+bit: csrc/mesh_smooth.hip, sdfr_mesh_smooth_*; smooth_lattice its default lattice;
+mesh_boundary the valences and boundary flags; extract_mesh_sparse(smooth=n) smooths before
+the host copy);
 rasterize_mesh -> Raster (B views of a Mesh, nearest
 triangle per pixel with depth and perspective-correct barycentrics, deterministic:
 csrc/raster.hip, sdfr_mesh_raster), interpolate_vertex_attributes (sdfr_mesh_interpolate),
@@ -48,13 +52,13 @@ from .generator import (Blur, Decoder, EqualLinear, FusedLeakyReLU, Generator,  
                         MappingLinear, ModulatedConv2d, NoiseInjection, PixelNorm, StyledConv,
                         ToRGB, Upsample, fused_leaky_relu, make_kernel, upfirdn2d)
 from .graphs import GraphedGenerator  # noqa: F401
-from .mesh import (Components, Mesh, Simplified, SparseVolume, align_volume,  # noqa: F401
-                   color_mesh,
+from .mesh import (Components, Mesh, Simplified, Smoothed, SparseVolume,  # noqa: F401
+                   align_volume, color_mesh,
                    component_stats, cube_axis, cube_points, eikonal_residual,
                    extract_mesh_sparse, extract_mesh_with_marching_cubes, keep_components,
-                   label_components, marching_cubes, mesh_components, normal_mesh, sdf_cube,
-                   shade_surface, simplify_grid, simplify_mesh, sparse_extract, sparse_mesh,
-                   world_to_network, xyz2mesh)
+                   label_components, marching_cubes, mesh_boundary, mesh_components, normal_mesh,
+                   sdf_cube, shade_surface, simplify_grid, simplify_mesh, smooth_lattice,
+                   smooth_mesh, sparse_extract, sparse_mesh, world_to_network, xyz2mesh)
 from .raster import (Raster, interpolate_vertex_attributes, load_obj, rasterize_mesh,  # noqa: F401
                      render_mesh, subdivide_mesh)
 from .options import AttrDict, SDFOptions, vol_render_opt  # noqa: F401

@@ -330,6 +330,10 @@ PROTOTYPES = {
                                         _u32, _int, _vp, _sz, _P(_u32), _vp]),
     "sdfr_mesh_simplify_emit": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp, _vp, _vp,
                                        _vp, _vp, _vp]),
+    "sdfr_mesh_smooth_workspace_bytes": (_sz, [_u32] * 2),
+    "sdfr_mesh_smooth_prepare": (_int, [_vp, _vp, _u32, _u32, _f32, _f32, _f32, _int, _int, _vp,
+                                        _sz, _vp, _vp, _vp]),
+    "sdfr_mesh_smooth_run": (_int, [_vp, _u32, _P(_f32), _u32, _vp, _sz, _vp, _vp]),
     "sdfr_mesh_raster_workspace_bytes": (_sz, [_u32] * 5),
     "sdfr_mesh_raster": (_int, [_P(RasterArgs), _vp]),
     "sdfr_mesh_interpolate": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32,

@@ -680,8 +680,9 @@ class Generator(nn.Module):
         mapping network and truncation of ``query_field``, then ``mesh.extract_mesh_sparse``
         (``kw``: level, lipschitz, grow, return_volume, components -- e.g.
         ``components={"largest": 1}`` keeps the largest connected component -- and simplify:
-        ``simplify=4`` clusters the vertices of 4^3 lattice cells on the GPU before the copy)
-        -> ``Mesh``."""
+        ``simplify=4`` clusters the vertices of 4^3 lattice cells on the GPU before the copy,
+        and smooth: ``smooth=10`` runs 10 Taubin iterations of ``mesh.smooth_mesh`` on the GPU
+        after that, or a dict of its keyword arguments) -> ``Mesh``."""
         from .mesh import extract_mesh_sparse
         lat0 = self._renderer_latent(styles, truncation, truncation_latent, input_is_latent)
         return extract_mesh_sparse(self.renderer, lat0, res=res, **kw)

@@ -678,8 +678,170 @@ def _check_simplify_factor(simplify, what):
     return int(simplify)
 
 
+Smoothed = namedtuple("Smoothed", ("verts", "valence", "boundary"))
+Smoothed.__doc__ = """A mesh smoothed on the GPU (``smooth_mesh``): ``verts`` [V, 3] fp32 (the
+faces are the input's), ``valence`` [V] int32 (face corners per vertex) and ``boundary`` [V]
+bool (the vertex is an end of an edge that exactly one face has)."""
+
+_SMOOTH_UNIT_LOG2 = (-126, 96)
+
+
+def smooth_lattice(lo, hi):
+    """The default lattice of ``smooth_mesh`` for a bounding box ``lo`` .. ``hi`` (three numbers
+    each, fp32 values): ``(origin, unit_log2)``.  The origin is ``lo``; with E the longest
+    edge of the box (in float64; 0 is taken as 1) written as m 2^x, m in [0.5, 1),
+    ``unit_log2 = x - 30``: the box spans at most 2^30 units of 2^unit_log2.  ValueError for a
+    box that is not finite, or whose unit would leave [-126, 96]."""
+    import math
+    lo = [float(np.float32(x)) for x in lo]
+    hi = [float(x) for x in hi]
+    if len(lo) != 3 or len(hi) != 3 or not np.isfinite(lo + hi).all():
+        raise ValueError("smooth_mesh: a vertex coordinate is not finite")
+    extent = max(h - l for l, h in zip(lo, hi))
+    if not extent > 0:
+        extent = 1.0
+    unit_log2 = math.frexp(extent)[1] - 30
+    _check_smooth_unit(unit_log2)
+    return tuple(lo), unit_log2
+
+
+def _check_smooth_unit(unit_log2):
+    if isinstance(unit_log2, bool) or int(unit_log2) != unit_log2 or \
+            not _SMOOTH_UNIT_LOG2[0] <= unit_log2 <= _SMOOTH_UNIT_LOG2[1]:
+        raise ValueError(f"smooth_mesh: unit_log2 must be an integer in [-126, 96], not "
+                         f"{unit_log2!r}")
+
+
+def _smooth_check(rc: int, what: str):
+    """``_lib.check``, with the device-side findings as ValueError."""
+    from . import _lib
+    if rc == _lib.SDFR_EINVAL:
+        msg = _lib.lib().sdfr_last_error().decode(errors="replace")
+        if "outside [0," in msg or "not finite" in msg or "outside the lattice" in msg:
+            raise ValueError(f"{what}: {msg}")
+    _lib.check(rc, what)
+
+
+def _smooth_schedule(iterations, lam, mu):
+    """The pass weights of ``smooth_mesh``: ``iterations`` times (lam,) or (lam, mu)."""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) \
+            or iterations < 0:
+        raise ValueError(f"smooth_mesh: iterations must be an integer >= 0, not {iterations!r}")
+    if not (np.isfinite(lam) and 0 < lam <= 1):
+        raise ValueError(f"smooth_mesh: lam must be in (0, 1], not {lam!r}")
+    if mu is not None and not (np.isfinite(mu) and -1 <= mu <= 0):
+        raise ValueError(f"smooth_mesh: mu must be None or in [-1, 0], not {mu!r}")
+    one = [float(lam)] if mu is None or mu == 0 else [float(lam), float(mu)]
+    weights = one * int(iterations)
+    if len(weights) > 1024:
+        raise ValueError(f"smooth_mesh: {len(weights)} passes; at most 1024 in one call")
+    return weights
+
+
+def _smooth_prepare(what, verts, faces, origin, unit_log2, pin_boundary):
+    """``sdfr_mesh_smooth_prepare`` -> (workspace, its size, valence, boundary)."""
+    from . import _lib
+    if (origin is None) != (unit_log2 is None):
+        raise ValueError(f"{what}: give both origin and unit_log2 (the lattice), or neither")
+    if origin is None:
+        lo, hi = (t.cpu().tolist() for t in verts.aminmax(dim=0))
+        origin, unit_log2 = smooth_lattice(lo, hi)
+    else:
+        origin = tuple(float(x) for x in origin)
+        if len(origin) != 3 or not np.isfinite(origin).all():
+            raise ValueError(f"{what}: origin must be three finite numbers, got {origin}")
+        _check_smooth_unit(unit_log2)
+    L = _lib.lib()
+    dev = verts.device
+    V, F = verts.shape[0], faces.shape[0]
+    n = L.sdfr_mesh_smooth_workspace_bytes(V, F)
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    valence = torch.empty(V, dtype=torch.int32, device=dev)
+    boundary = torch.empty(V, dtype=torch.bool, device=dev)
+    _smooth_check(L.sdfr_mesh_smooth_prepare(
+        _lib.ptr(verts), _lib.ptr(faces), V, F, origin[0], origin[1], origin[2], int(unit_log2),
+        int(bool(pin_boundary)), _lib.ptr(ws), n, _lib.ptr(valence), _lib.ptr(boundary),
+        _lib.stream_of(verts)), what)
+    return ws, n, valence, boundary
+
+
+def mesh_boundary(mesh_or_verts, faces=None):
+    """``(valence, boundary)`` of a mesh, on the GPU (``sdfr_mesh_smooth_prepare`` alone):
+    ``valence`` [V] int32, the number of face corners at each vertex, and ``boundary`` [V]
+    bool, whether the vertex is an end of an edge that exactly one face has.
+    ``boundary.any()`` answers "is this mesh open?" -- for the field's mesh, whether the level
+    set left the cube.  A ``Mesh`` gives NumPy arrays, device tensors give device tensors.
+    ValueError for a face index outside [0, V) or a non-finite coordinate."""
+    what = "mesh_boundary"
+    verts, faces, mesh = _cc_inputs(what, mesh_or_verts, faces)
+    _, _, valence, boundary = _smooth_prepare(what, verts, faces, None, None, True)
+    if mesh is None:
+        return valence, boundary
+    return valence.cpu().numpy(), boundary.cpu().numpy()
+
+
+def smooth_mesh(mesh_or_verts, faces=None, *, iterations=10, lam=0.5, mu=-0.53,
+                pin_boundary=True, origin=None, unit_log2=None):
+    """The mesh smoothed by Laplacian or Taubin lambda | mu passes of the uniform umbrella
+    operator, on the GPU (csrc/mesh_smooth.hip, ``sdfr_mesh_smooth_prepare`` / ``_run``;
+    include/sdfr.h, "Mesh smoothing") -- where users of the reference call trimesh's
+    ``filter_taubin`` / ``filter_laplacian`` on the host.  The vertices are quantised to an
+    integer lattice and the passes run on integers, so the result is reproducible bit for
+    bit, whatever the order of the faces.
+
+    ``iterations`` times a pass of weight ``lam`` followed by one of weight ``mu`` (Taubin:
+    the second pass undoes the shrinkage of the first); ``mu=None`` or ``mu=0`` gives
+    Laplacian passes of weight ``lam`` alone.  ``pin_boundary`` keeps the vertices on an open
+    mesh's border where they are.  ``origin`` (three numbers) and ``unit_log2`` (an integer in
+    [-126, 96]) fix the lattice of spacing 2^unit_log2, on which every vertex must lie within
+    [0, 2^30] units of the origin per axis; without them it is ``smooth_lattice`` of the
+    bounding box.  ``iterations=0`` returns the input's bits, and a vertex that no face
+    references or that is pinned always keeps them.
+
+    A ``Mesh`` (host arrays) gives a new ``Mesh`` with the same faces; its ``vertex_colors`` /
+    ``vertex_normals`` are carried over unchanged (the indexing is the same) -- call
+    ``color_mesh`` / ``normal_mesh`` again for the field's values at the moved vertices.
+    ``verts`` [V, 3] fp32 and ``faces`` [F, 3] int32 | int64 on the GPU give a ``Smoothed``
+    named tuple, all on the GPU.
+
+    ValueError for bad selectors (``iterations`` negative or not an integer, ``lam`` not in
+    (0, 1], ``mu`` not in [-1, 0]), half a lattice, a face index outside [0, V), a
+    non-finite coordinate, or a vertex outside the lattice.  There is no CPU path."""
+    from . import _lib
+    what = "smooth_mesh"
+    weights = _smooth_schedule(iterations, lam, mu)
+    verts, faces, mesh = _cc_inputs(what, mesh_or_verts, faces)
+    ws, n, valence, boundary = _smooth_prepare(what, verts, faces, origin, unit_log2,
+                                               pin_boundary)
+    out = torch.empty_like(verts)
+    w = (_lib._f32 * max(len(weights), 1))(*weights)
+    _smooth_check(_lib.lib().sdfr_mesh_smooth_run(
+        _lib.ptr(verts), verts.shape[0], w, len(weights), _lib.ptr(ws), n, _lib.ptr(out),
+        _lib.stream_of(verts)), what)
+    if mesh is None:
+        return Smoothed(out, valence, boundary)
+    return Mesh(out.cpu().numpy(), mesh.faces, mesh.vertex_colors, mesh.vertex_normals)
+
+
+def _check_smooth(smooth, what):
+    """``smooth`` of ``sparse_mesh``: None, or the keyword arguments of ``smooth_mesh``."""
+    if smooth is None:
+        return None
+    if isinstance(smooth, dict):
+        kw = dict(smooth)
+        if "origin" in kw or "unit_log2" in kw:
+            raise ValueError(f"{what}: smooth takes no lattice: it is that of res")
+    elif isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)):
+        raise ValueError(f"{what}: smooth must be None, an integer (Taubin iterations) or a "
+                         f"dict of smooth_mesh keyword arguments, not {smooth!r}")
+    else:
+        kw = {"iterations": int(smooth)}
+    _smooth_schedule(kw.get("iterations", 10), kw.get("lam", 0.5), kw.get("mu", -0.53))
+    return kw
+
+
 def sparse_mesh(evaluate, axes, res: int, seeds: torch.Tensor, level: float = 0.0,
-                grow: bool = True, components=None, simplify=None):
+                grow: bool = True, components=None, simplify=None, smooth=None):
     """``sparse_extract`` and ``extract_mesh_sparse``'s finish: ``(Mesh, SparseVolume)`` with
     the vertices scaled to (v / res - 0.5) * 0.24 per axis and y, z negated, on the host.
     ``components``: ``None``, or a dict of ``keep_components`` keyword arguments that filters
@@ -687,14 +849,22 @@ def sparse_mesh(evaluate, axes, res: int, seeds: torch.Tensor, level: float = 0.
     kept is copied).  ``simplify``: ``None``, or an integer k >= 2: after that filter (a floater
     is never merged into the face) and before the scaling and the copy, ``simplify_mesh`` in
     index coordinates on the grid of origin 0, cell k and ceil(res / k) cells per axis -- a
-    function of ``res`` and k alone, not of the mesh."""
+    function of ``res`` and k alone, not of the mesh.  ``smooth``: ``None``, an integer (that
+    many Taubin iterations with ``smooth_mesh``'s defaults) or a dict of ``smooth_mesh``
+    keyword arguments: after the two steps above and before the scaling and the copy,
+    ``smooth_mesh`` in index coordinates on the lattice ``smooth_lattice((0, 0, 0), (res, res,
+    res))`` -- a function of ``res`` alone, so no bounding box is computed."""
     simplify = _check_simplify_factor(simplify, "sparse_mesh")
+    smooth = _check_smooth(smooth, "sparse_mesh")
     verts, faces, volume = sparse_extract(evaluate, axes, res, seeds, level, grow)
     if components is not None:
         verts, faces, _ = keep_components(verts, faces, **components)
     if simplify is not None:
         verts, faces = simplify_mesh(verts, faces, cell=float(simplify), origin=(0.0, 0.0, 0.0),
                                      dims=(-(-res // simplify),) * 3)[:2]
+    if smooth is not None:
+        origin, unit_log2 = smooth_lattice((0.0,) * 3, (float(res),) * 3)
+        verts = smooth_mesh(verts, faces, origin=origin, unit_log2=unit_log2, **smooth).verts
     for axis in range(3):
         verts[:, axis] = (verts[:, axis] / float(res) - 0.5) * 0.24
     verts[:, 2] *= -1
@@ -704,7 +874,7 @@ def sparse_mesh(evaluate, axes, res: int, seeds: torch.Tensor, level: float = 0.
 
 def extract_mesh_sparse(renderer, styles: torch.Tensor, res: int = 512, level: float = 0.0,
                         lipschitz=None, grow: bool = True, return_volume: bool = False,
-                        components=None, simplify=None):
+                        components=None, simplify=None, smooth=None):
     """The ``level`` set of the field itself at ``res``^3 without the dense cube: the
     ``Mesh`` that ``extract_mesh_with_marching_cubes(sdf_cube(renderer, styles, res))``
     gives (same vertex scaling and y / z flips, the same triangles with bit-equal
@@ -734,10 +904,17 @@ def extract_mesh_sparse(renderer, styles: torch.Tensor, res: int = 512, level: f
     vertex clustering (``simplify_mesh``) with k lattice cells per cluster cell, on the GPU,
     after the ``components`` filter and before the vertex scaling and the copy to the host --
     about 1 / k^2 of the vertices and faces are copied.  The grid depends on ``res`` and k
-    only.  Not promised: manifoldness and sharp features (see ``simplify_mesh``)."""
+    only.  Not promised: manifoldness and sharp features (see ``simplify_mesh``).
+
+    ``smooth``: ``None`` (no smoothing), an integer n (n Taubin iterations with
+    ``smooth_mesh``'s defaults) or a dict of ``smooth_mesh`` keyword arguments: the mesh is
+    smoothed on the GPU after ``components`` and ``simplify`` and before the vertex scaling
+    and the copy -- it takes off the facets that clustering prints onto the surface and the
+    hash grid's high-frequency bumps.  The lattice depends on ``res`` only."""
     if styles.shape[0] != 1:
         raise ValueError("extract_mesh_sparse: one mesh, one face (styles [1, 256])")
     simplify = _check_simplify_factor(simplify, "extract_mesh_sparse")
+    smooth = _check_smooth(smooth, "extract_mesh_sparse")
     nb = _check_brick_res(res, "extract_mesh_sparse")
     if not styles.is_cuda:
         raise RuntimeError("extract_mesh_sparse: needs the GPU (HIP kernels)")
@@ -759,7 +936,7 @@ def extract_mesh_sparse(renderer, styles: torch.Tensor, res: int = 512, level: f
         band = float(lipschitz) * 4.0 * (3.0 ** 0.5) * (2.0 / res)
         seeds = (sdf_c.reshape(-1).float() - level).abs() <= band
         mesh, volume = sparse_mesh(evaluate, axes, res, seeds, level, grow, components,
-                                   simplify)
+                                   simplify, smooth)
     return (mesh, volume) if return_volume else mesh
 
 
